@@ -2,6 +2,11 @@
 """Benchmark of the VIC hot path (dist_prec -> full_energy -> surface_fluxes) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg4|cfg2] [--compat] [--node-solver newton|brent]
+                    [--dump-outputs DIR]
+
+K is the number of timed steps (cfg5: a multiple of 24, whole output records); `ms_per_step` in the JSON line is the wall
+time of the timed region over K.  `--dump-outputs DIR` writes what the timed path computed (bench.dump_outputs) as .npy
+files; the inputs depend on the arguments only, so two builds can be compared output for output.
 
 A "step" is one model time step of every cell of the rank's shard (all HRUs, all snow sub-steps) INCLUDING its put_data
 (dist_prec.c:167): the aggregated output variables are updated on the device every step, and the table the writer needs
@@ -179,6 +184,64 @@ def valu_roofline(config_name, cell_steps_per_s):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_CELLS = 100000     # per-cell arrays of larger domains: a fixed, seeded sample of the cells
+DUMP_MAX_HRUS = 16384       # the state: a fixed, seeded sample of the HRUs
+DUMP_SEED = 1234
+
+
+def dump_sample(n, cap, seed):
+    """Sorted indices of a fixed sample of range(n) (all of it when n <= cap)."""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def split_undefined(name, a):
+    """{name: a} when `a` holds no NaN.  NaN in the state and outputs marks a quantity that does not exist for that HRU or cell
+    (SD_GLAC_CUM_MASS_BALANCE before the driver opens a glacier's accumulation window, a frost / thaw front that is not
+    there), not a computed value: such an array is written with those entries as 0 next to `<name>_defined` (float32, 1 where
+    the value exists).  Infinities are left as they are."""
+    import numpy as np
+    nan = np.isnan(a)
+    if not nan.any():
+        return {name: a}
+    return {name: np.where(nan, 0, a).astype(a.dtype), name + "_defined": (~nan).astype(np.float32)}
+
+
+def dump_outputs(dirname, m, table):
+    """`--dump-outputs DIR`: what the timed path handed its caller after its last step, as DIR/<name>.npy -- the writer's
+    table (`table`, float32 [rows][cells], as fetched after the timed region), the output variables of the last step, the cell
+    accumulators and error flags (float64 [rows][cells]) and the model state (float64 [rows][HRUs]; the integer rows as
+    float64) of model `m`, NaN markers split off by split_undefined.  Index arrays name the sampled cells / HRUs.  Called
+    before `m` is closed or stepped again."""
+    import numpy as np
+    cols = dump_sample(table.shape[1], DUMP_MAX_CELLS, DUMP_SEED)
+    cells = dump_sample(m.dom.ncell, DUMP_MAX_CELLS, DUMP_SEED)
+    hrus = dump_sample(m.dom.nhru, DUMP_MAX_HRUS, DUMP_SEED + 1)
+    sd, si = m.get_state()
+    arrays = {
+        "output_table": np.ascontiguousarray(table[:, cols], dtype=np.float32),
+        "output_table_cells": cols.astype(np.float64),
+        "output_last_step": m.get_output_data(OUT_VARS, aggregated=False)[:, cells],
+        "cell_accum": m.get_accum()[:, cells],
+        "cell_error_flags": m.get_cell_errors()[cells].astype(np.float64),
+        "cells": cells.astype(np.float64),
+        "state_double": np.ascontiguousarray(sd[:, hrus]),
+        "state_int": si[:, hrus].astype(np.float64),
+        "hrus": hrus.astype(np.float64),
+    }
+    del sd, si
+    arrays = {k: v for name, a in arrays.items() for k, v in split_undefined(name, a).items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -260,8 +323,7 @@ def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_di
     from vic_amd.api import Model
     opt = cfg["opt"]
     K, W, CH = args.steps, args.warmup, 6
-    K = max(OUT_STEP_RATIO, (K // OUT_STEP_RATIO) * OUT_STEP_RATIO)             # whole output records
-    W = (W // CH) * CH
+    assert K % OUT_STEP_RATIO == 0 and W % CH == 0                               # whole output records, whole chunks
 
     def barrier():
         torch.cuda.synchronize()
@@ -317,6 +379,8 @@ def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_di
     kernel_ms, nlaunch = m.last_kernel_ms()
     same = all(np.array_equal(a, b, equal_nan=True) for a, b in zip(m.get_state(), state_ref))
     nerr = int((m.get_cell_errors() != 0).sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, tables[-1])
     # one chunk's upload + derivation on its own
     fs = f[W:W + CH]
     for name, src, scale in RAW_FROM_TABLE:
@@ -374,7 +438,14 @@ def main():
     ap.add_argument("--ncell", type=int, default=0, help="override cells per GPU (debug only; invalidates the metric)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (the writer's output table, the last step's "
+                         "output values, cell accumulators and error flags, a fixed sample of the state) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.config == "cfg5" and args.steps % OUT_STEP_RATIO:
+        raise SystemExit("--config cfg5 times whole output records: --steps must be a multiple of %d" % OUT_STEP_RATIO)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))        # nothing above has touched the GPU
@@ -411,8 +482,7 @@ def main():
     opt.NODE_SOLVER = C["VIC_NODE_SOLVER_NEWTON"] if args.node_solver == "newton" else C["VIC_NODE_SOLVER_BRENT"]
     ncell = args.ncell or cfg["ncell"]
     K, W = args.steps, args.warmup
-    if cfg_name == "cfg5":                # whole output records and whole forcing chunks
-        K = args.steps = max(OUT_STEP_RATIO, (K // OUT_STEP_RATIO) * OUT_STEP_RATIO)
+    if cfg_name == "cfg5":                # whole forcing chunks in the warm-up (the timed steps are whole output records)
         W = args.warmup = (W // 6) * 6
     # ONE domain of world x ncell cells, cut into contiguous HRU-balanced blocks (shard.partition_cells: every cell has the
     # same number of HRUs here, so the blocks are equal); this rank builds only its block
@@ -485,6 +555,8 @@ def main():
         nerr_t = torch.tensor([nerr], device="cuda", dtype=torch.int64)
         dist.all_reduce(nerr_t)
         nerr = int(nerr_t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, full)
     # the same K steps with the other node solver (N = 1): what the choice of solver costs / buys
     other_ms = None
     if world == 1 and not opt.QUICK_FLUX and not args.no_strict_leg:
