@@ -734,10 +734,10 @@ def test_month_long_trajectory(solver, oracle_lib):
     """A month of hourly steps through the spring thaw (every frozen-node pattern, rain on snow, melt-out), the GPU running
     freely.  The model is discontinuous in its state (a Brent bracket that just fails, a fallback, a regime switch): over
     hundreds of steps two correct implementations that differ in the last digits drift apart at such points -- here
-    1e-9 relative for 560 steps, then one HRU takes another branch (tools/exp/diverge.py; the oracle started from the
-    GPU's own state reproduces the GPU's next step to 1e-12).  So the long run is checked along the GPU's OWN trajectory:
-    every 12 hours the oracle is put on the GPU's state and both take the next step (1e-6 relative on every state row),
-    and the freely running oracle's accumulated outputs must still agree to 1e-4."""
+    1e-9 relative for 560 steps, then one HRU takes another branch (`git show df5216f:tools/exp/diverge.py`; the oracle
+    started from the GPU's own state reproduces the GPU's next step to 1e-12).  So the long run is checked along the GPU's
+    OWN trajectory: every 12 hours the oracle is put on the GPU's state and both take the next step (1e-6 relative on every
+    state row), and the freely running oracle's accumulated outputs must still agree to 1e-4."""
     from vic_amd.api import Model
     kw = dict(FULL_ENERGY=1, FROZEN_SOIL=1, Nnode=10, Nband=2, frozen_compat=0, NODE_SOLVER=SOLVERS[solver])
     nsteps, every = 720, 12

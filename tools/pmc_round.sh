@@ -1,7 +1,7 @@
 # PMC passes over one bench workload at full size (run on the GPU box: gpurun -- 'bash tools/pmc_round.sh').  Counters only
 # (--kernel-trace for the names; no other trace domain).  Output: gpurun_out/${PMC_DIR:-pmc}/passN/, summary by tools/pmc_summary.py.
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${PMC_DIR:-pmc}; mkdir -p $O
 ARGS=${BENCH_ARGS:---steps 2 --warmup 1 --no-cpu-baseline --no-strict-leg --no-stream-leg --no-compat-leg}
 PASSES=${PASSES:-"1 2 3"}

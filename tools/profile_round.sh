@@ -2,8 +2,8 @@
 # 1) kernel trace + stats of `bench.py` (the command the bench line comes from), 2) HBM traffic: FETCH_SIZE and WRITE_SIZE in
 # separate PMC passes (they do not fit one pass on gfx950), 3) SQ counters (lanes active, VALU share), 4) the FETCH_SIZE
 # calibration kernels (tools/calib/).  Counters and traces never share a pass.  Output under gpurun_out/${ROUND_DIR:-round}/.
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${ROUND_DIR:-round}
 rm -rf $O && mkdir -p $O
 ARGS=${BENCH_ARGS:---steps 6 --warmup 2 --no-cpu-baseline --no-strict-leg --no-stream-leg --no-compat-leg}

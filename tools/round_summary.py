@@ -3,15 +3,15 @@
 
   profiles/rNN_<config>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of the bench command
   profiles/traffic_<config>.json           HBM bytes per step from the FETCH_SIZE / WRITE_SIZE passes, stamped with the digest of
-                                           the device sources it was measured on (bench.py reads it and refuses a stale one);
-  profiles/rNN_traffic_<config>.json       the same file, kept per round
+                                           the device sources it was measured on (bench.py reads it and refuses a stale one)
 
 Units and corrections (MI355X_MICROARCH.md, HBM section): both counters are in KiB; on gfx950 FETCH_SIZE reports half the
 bytes of a 16-byte-per-lane streaming read.  The factor applied to the reads of these kernels is the one MEASURED for their
 access patterns by tools/calib/fetch_calib.hip in the same gpurun call (gpurun_out/<round>/calib -> profiles/fetch_calibration.json):
 wave slabs read 16 bytes per lane (parked context: stage, evaluation and put_data kernels) and per-lane contiguous blocks
 (item blocks: profile kernels); 2.0 where no calibration is at hand.  Also written: profiles/pmc_<config>.json, lanes active
-per vector instruction and the VALU-active share of the wave cycles over the pipeline's kernels (SQ pass).
+per vector instruction and the VALU-active share of the wave cycles over the pipeline's kernels (SQ pass).  Both JSON files
+hold the latest measurement only; git history keeps those of earlier rounds.
 
     python tools/round_summary.py r02 cfg3 100000 8 [_compat]   # round tag, config, cells per GPU, steps launched (warmup + timed)
 """
@@ -69,9 +69,8 @@ out = {"config": config, "cells_per_gpu": ncell, "steps_profiled": nsteps, "roun
                        "source": "profiles/fetch_calibration.json" if calib else "MI355X_MICROARCH.md (uncalibrated for these patterns)"},
        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (tools/profile_round.sh); KiB -> bytes; "
                  "reads x the factor measured for the kernel's access pattern (tools/calib/fetch_calib.hip)"}
-for name in ("traffic_%s%s.json" % (config, suffix), "%s_traffic_%s%s.json" % (tag, config, suffix)):
-    with open(os.path.join(dst, name), "w") as f:
-        json.dump(out, f, indent=1)
+with open(os.path.join(dst, "traffic_%s%s.json" % (config, suffix)), "w") as f:
+    json.dump(out, f, indent=1)
 print(json.dumps(out, indent=1))
 # SQ pass -> lanes active / VALU share over the pipeline's kernels
 sqf = os.path.join(src, "sq", "p_counter_collection.csv")
@@ -96,7 +95,6 @@ if sqs:
                              "valu_active_share_of_wave_cycles": v["SQ_ACTIVE_INST_VALU"] / max(v["SQ_WAVE_CYCLES"], 1),
                              "valu_insts_per_step": v["SQ_INSTS_VALU"] / nsteps} for k, v in perk.items()},
           "method": "rocprofv3 --pmc SQ_* (tools/profile_round.sh), summed over the dispatches of the bench command"}
-    for name in ("pmc_%s%s.json" % (config, suffix), "%s_pmc_%s%s.json" % (tag, config, suffix)):
-        with open(os.path.join(dst, name), "w") as f:
-            json.dump(pj, f, indent=1)
+    with open(os.path.join(dst, "pmc_%s%s.json" % (config, suffix)), "w") as f:
+        json.dump(pj, f, indent=1)
     print(json.dumps({k: v for k, v in pj.items() if k != "per_kernel"}, indent=1))

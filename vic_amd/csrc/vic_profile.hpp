@@ -37,10 +37,7 @@ namespace vic {
 // Work lists are kept in NBUCKET segments by a per-HRU key (the number of frozen nodes at the start of the step, and
 // whether a node sits within SOIL_DT of 0 C -- see vic_fd_stage): the profile kernel takes the segments one after the
 // other, most expensive first, so that the HRUs a wave works on at any time have the same nodes frozen.
-#ifndef PROFILE_NBUCKET
-#define PROFILE_NBUCKET (2 * (VIC_MAX_NODES + 2))
-#endif
-constexpr int NBUCKET = PROFILE_NBUCKET;
+constexpr int NBUCKET = 2 * (VIC_MAX_NODES + 2);
 static_assert(NBUCKET <= 64, "one lane per work-list segment when the pending total is summed");
 
 struct PArgs {
@@ -71,28 +68,13 @@ __host__ __device__ inline int pout_stride(int Nn) { return Nn + 1 + (Nn + 1) / 
 __host__ __device__ inline int pout_hru_stride(int Nn) { return 2 * pout_stride(Nn) + 2; }
 __host__ __device__ inline int pout_key(int Nn, int slot) { return 2 * pout_stride(Nn) + slot; }
 
-#ifndef LOCKSTEP_GATE_LANES
-#define LOCKSTEP_GATE_LANES 16
-#endif
-constexpr int LOCKSTEP_GATE = LOCKSTEP_GATE_LANES;   // idle lanes that must be waiting before the write-back / fetch section runs
+constexpr int LOCKSTEP_GATE = 16;   // idle lanes that must be waiting before the write-back / fetch section runs
 
 constexpr double NODE_ROOT_RANGE = SOIL_DT + Brent::MAXTRIES * Brent::TSTEP;   // the reference finds roots within T0 +- this
 constexpr double NODE_NEWTON_TOL = 1.e-8;                                        // last Newton step, K
-#ifndef VIC_NEWTON_PREDICTOR
-#define VIC_NEWTON_PREDICTOR 1
-#endif
-#ifndef VIC_NOSE_CLASSIFY
-#define VIC_NOSE_CLASSIFY 1
-#endif
-#ifndef VIC_PREDICT_TOL2
-#define VIC_PREDICT_TOL2 1.e-7
-#endif
-#ifndef VIC_NEWTON_ACCEPT
-#define VIC_NEWTON_ACCEPT 2.e-11
-#endif
-constexpr double NODE_PREDICT_TOL2 = VIC_PREDICT_TOL2;    // the predictor stops when step^2 <= this * |T| (its error is then < 1e-6 K)
+constexpr double NODE_PREDICT_TOL2 = 1.e-7;   // the predictor stops when step^2 <= this * |T| (its error is then < 1e-6 K)
 constexpr int NODE_PREDICT_MAXIT = 12;
-constexpr double NODE_NEWTON_ACCEPT = VIC_NEWTON_ACCEPT;  // (1 + |Y|) s^2 / |T| below this: the error left after the step is below 1e-11 K
+constexpr double NODE_NEWTON_ACCEPT = 2.e-11; // (1 + |Y|) s^2 / |T| below this: the error left after the step is below 1e-11 K
 constexpr int NODE_NEWTON_MAXIT = 200;
 
 // The per-node constants of one record (PR_AT0 .. PR_EMM), see vic_surface.hpp
@@ -128,28 +110,17 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
   // `steep`: visits that run the reference's Brent iteration -- all frozen visits when NEWTON is off, otherwise only the
   // discontinuous cold-nose case at node 1
   bool steep = false;
-#ifdef VIC_ABL_NONOSE          // ablation builds (tools/exp): wrong results, they only attribute time
-  const bool nose = false;
-#else
   const bool nose = NODE1 && fabs(Tdn - Tup) > 5.;
-#endif
   if (!NEWTON) steep = fz;
-#if !VIC_NOSE_CLASSIFY
-  else if (NODE1) steep = fz && nose;
-#endif
   double x = N / K.S;                       // unfrozen node, or root in T >= 0 where ice = 0
   failed = false;
   PROF_WAVE(18); PROF_VOTE(19, fz);
 
   // ---- safeguarded Newton on f(T) = N - S T + E ice(T) in T < 0 (f(0) = N < 0 there: 0 is an upper bound of the root)
   bool act = NEWTON && fz && !steep && N < 0;
-#ifdef VIC_ABL_NONEWTON
-  act = false;
-#endif
   if (NEWTON && __any(act)) {
     PROF_WAVE(22);
     x = act ? oldT : x;
-#if VIC_NEWTON_PREDICTOR
     // Predictor: the same Newton iteration with the freezing curve through the hardware's single-precision log2 / exp2
     // (relative error ~3e-7, ~35 instructions per iteration instead of ~130) until the step is small enough for the
     // double-precision iteration below to finish in one evaluation.  It only moves the starting point: its bracket is its
@@ -185,7 +156,6 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
       }
       PROF_ADD(22, t_pre);
     }
-#endif
     double lo = -1.e300, hi = 0.0;
     int it = 0;
     PROF_T0(t_nw);
@@ -198,15 +168,10 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
         const double f = N - K.S * x + Ei;
         if (f > 0) lo = x; else hi = x;
         const double den = K.S * x + (curved ? K.Y * Eu : 0.0);          // = x f'(x), negative
-#if VIC_NEWTON_PREDICTOR
         const double step = f * x * rcp_refined(den);                     // a step's last digits do not matter (see below)
-#else
-        const double step = f * x / den;
-#endif
         double xn = x + step;
         it++;
         if (fabs(step) <= NODE_NEWTON_TOL) act = false;                      // converged: the step is taken as it is
-#if VIC_NEWTON_PREDICTOR
         // On the smooth branch of the curve the error left after a Newton step s is |f''/(2 f')| s^2 <= (1 + |Y|) s^2 / (2 |x|)
         // (f' = -S - Y Eu / x, f'' = -Y (Y - 1) Eu / x^2, |x| the smaller end of the step: |s| <= 0.05 |x| keeps it within 5 %,
         // the bound below has that margin).  When that bound is below the tolerance and the step stays
@@ -214,7 +179,6 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
         // an upper bound for small steps), the step is taken without another evaluation to confirm it.
         else if (curved && fabs(step) <= 0.05 * fabs(x) && (1. + fabs(K.Y)) * step * step <= NODE_NEWTON_ACCEPT * fabs(x)
                  && Eu * (1. + 2.2 * fabs(K.Y * step) * rcp_refined(fabs(x))) < K.EM) act = false;
-#endif
         else {
           // a step that leaves the bracket (a kink of the curve between x and the root) is replaced by a bisection; a step
           // down can only leave it once a lower bound is known
@@ -226,7 +190,6 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
     }
     PROF_ADD(23, t_nw);
   }
-#if VIC_NOSE_CLASSIFY
   // ---- node 1, cold nose (soil_thermal_eqn.c:57-72, 84-93).  With |TL - TU| > 5 K the reference drops the flux term
   // ft1 = B (TL - TU) from the residual where ft1 < 0, T < min(TL, TU), ft2(T) > 0 and |ft1| > |ft2(T)|; ft2 decreases in T, so
   // that is an interval Tb < T < Thi below both neighbours (ft2 > 0 holds there by itself; EXP_TRANS: below its own zero as
@@ -249,7 +212,6 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
       steep = sp && Tb < Thi && !failed && x < Thi + 1.e-6;
     }
   }
-#endif
   // ---- the reference's Brent iteration (root_brent.c:97-337) on the reference's residual
   if (NODE1 || !NEWTON) {
     if (__any(steep)) {
@@ -277,9 +239,6 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
   }
   // the reference searches T0 +- 0.25 K, widened by 10 K up to five times (root_brent.c:183-248)
   if (fz && !steep && !(fabs(x - T0j) <= NODE_ROOT_RANGE)) failed = true;
-#ifdef VIC_DEBUG_NODE
-  if (failed) printf("node failed: NODE1 %d steep %d N %g S %g x %.17g T0j %g oldT %g Tdn %g Tup %g G %g Y %g EM %g EMM %g\n", (int)NODE1, (int)steep, N, K.S, x, T0j, oldT, Tdn, Tup, K.G, K.Y, K.EM, K.EMM);
-#endif
   return x;
 }
 
@@ -327,9 +286,7 @@ VIC_DEV int profile_pick(const PArgs& a, const int* bcount, int slot) {
 // ------------------------------------------------------------------------------------------------
 // 10 nodes (the sample global file's and BASELINE's node count): node constants and temperatures in registers
 // ------------------------------------------------------------------------------------------------
-#ifndef PROFILE_REG_WAVES
-#define PROFILE_REG_WAVES 2
-#endif
+constexpr int PROFILE_REG_WAVES = 2;
 template <int NN, bool NEWTON>
 __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG_WAVES) void vic_profile_solve_reg(const PArgs a) {
   __shared__ int bcount[NBUCKET];
@@ -487,9 +444,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
 // ------------------------------------------------------------------------------------------------
 // any node count: node columns in LDS, the node's record read at each visit
 // ------------------------------------------------------------------------------------------------
-#ifndef LS_WAVES
-#define LS_WAVES 2
-#endif
+constexpr int LS_WAVES = 2;
 template <int NN, bool NEWTON>
 __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_profile_solve_lockstep(const PArgs a) {
   __shared__ int bcount[NBUCKET];

@@ -123,43 +123,27 @@ struct KArgs {
 // while a dense wave still reads its slab front to back (its 16-byte accesses, 64 bytes apart, fill the same lines over four
 // instructions).  Measured, same box: evaluation kernel 6.8 vs 7.7-8.0 ms per step with the sparse rounds starting at 30 %
 // pending instead of 4 %; the opening stage, which WRITES the context, 4.7-4.9 vs 4.3-4.5 ms.  So the slab has two regions:
-// what the evaluation kernel reads (SurfSolve, SurfEBMut, SurfEBConst: words below CTX_NA) in groups of VIC_CTX_GROUP = 8, what
+// what the evaluation kernel reads (SurfSolve, SurfEBMut, SurfEBConst: words below CTX_NA) in groups of CTX_GROUP = 8, what
 // only the two stage kernels exchange (everything after) in pairs.  (G = 16 and 32 measure like 8, G = 4 worse than 2.)
-#ifndef VIC_CTX_AOS
-#define VIC_CTX_AOS 0
-#endif
-#ifndef VIC_CTX_GROUP
-#define VIC_CTX_GROUP 8
-#endif
-#ifndef VIC_CTX_GROUP_B
-#define VIC_CTX_GROUP_B 2
-#endif
-// Word W of HRU g:  AOS    [hru][word]                        one HRU's context is one contiguous block (measured in round 2:
-//                                                             sparse rounds -35 %, dense rounds +23 %)
-//                   else   region A [hru / 64][W / G][hru % 64][G], then region B the same with G_B and W - CTX_NA
+// (Not kept: one contiguous block per HRU, [hru][word], measured in round 2 against the slabs: sparse rounds -35 %, dense
+// rounds +23 %.)
+constexpr int CTX_GROUP = 8, CTX_GROUP_B = 2;
+// Word W of HRU g: region A [hru / 64][W / G][hru % 64][G], then region B the same with G_B and W - CTX_NA
 constexpr size_t CTX_NA = sizeof(SurfSolve) / 8 + sizeof(SurfEBMut) / 8 + offsetof(SurfEBConst, Cs2) / 8;
-constexpr size_t CTX_NA_PAD = (CTX_NA + VIC_CTX_GROUP - 1) / VIC_CTX_GROUP * VIC_CTX_GROUP;
+constexpr size_t CTX_NA_PAD = (CTX_NA + CTX_GROUP - 1) / CTX_GROUP * CTX_GROUP;
 constexpr size_t ctx_padded_words(size_t words) {      // slab words per lane
-  return CTX_NA_PAD + ((words > CTX_NA ? words - CTX_NA : 0) + VIC_CTX_GROUP_B - 1) / VIC_CTX_GROUP_B * VIC_CTX_GROUP_B;
+  return CTX_NA_PAD + ((words > CTX_NA ? words - CTX_NA : 0) + CTX_GROUP_B - 1) / CTX_GROUP_B * CTX_GROUP_B;
 }
 struct CtxRef {
-  unsigned long long* p;    // word 0 of this HRU (AOS) / of this HRU's wave slab
+  unsigned long long* p;    // word 0 of this HRU's wave slab
   int lane;
   VIC_DEV static CtxRef at(unsigned long long* base, size_t words_per_hru, size_t g) {
-#if VIC_CTX_AOS
-    return CtxRef{base + g * words_per_hru, 0};
-#else
     return CtxRef{base + (g >> 6) * (ctx_padded_words(words_per_hru) * 64), (int)(g & 63)};
-#endif
   }
   VIC_DEV unsigned long long* word(size_t W) const {
-#if VIC_CTX_AOS
-    return p + W;
-#else
-    if (W < CTX_NA) return p + (W / VIC_CTX_GROUP) * (64 * VIC_CTX_GROUP) + lane * VIC_CTX_GROUP + (W % VIC_CTX_GROUP);
+    if (W < CTX_NA) return p + (W / CTX_GROUP) * (64 * CTX_GROUP) + lane * CTX_GROUP + (W % CTX_GROUP);
     const size_t V = W - CTX_NA;
-    return p + CTX_NA_PAD * 64 + (V / VIC_CTX_GROUP_B) * (64 * VIC_CTX_GROUP_B) + lane * VIC_CTX_GROUP_B + (V % VIC_CTX_GROUP_B);
-#endif
+    return p + CTX_NA_PAD * 64 + (V / CTX_GROUP_B) * (64 * CTX_GROUP_B) + lane * CTX_GROUP_B + (V % CTX_GROUP_B);
   }
 };
 template <class T>
@@ -189,9 +173,6 @@ constexpr int EBM_W_FEED = offsetof(SurfEBMut, deltaCC) / 8, EBM_W_IN3 = offseto
               EBM_W_TSNOW = offsetof(SurfEBMut, ra_used) / 8, EBM_W_RA1 = EBM_W_TSNOW + 1, EBM_W_VV = offsetof(SurfEBMut, vv) / 8,
               EBM_W_KEEP = offsetof(SurfEBMut, Tnew2) / 8;
 static_assert(offsetof(SurfEBMut, fusion) / 8 == EBM_W_IN3 - 1 && offsetof(SurfEBMut, layerevap) / 8 == EBM_W_VV + 3, "SurfEBMut layout");
-#ifndef VIC_FINAL_SHORTCUT
-#define VIC_FINAL_SHORTCUT 1
-#endif
 constexpr size_t CW_SV = sizeof(SurfSolve) / 8, CW_EBM = sizeof(SurfEBMut) / 8, CW_EBC = EBC_W_CANOPY,      // Cs2 is never parked
                  CW_P = sizeof(SubStep) / 8, CW_L = sizeof(SubLoop) / 8, CW_C = sizeof(StepConst) / 8;
 constexpr size_t CO_SV = 0, CO_EBM = CO_SV + CW_SV, CO_EBC = CO_EBM + CW_EBM, CO_P = CO_EBC + CW_EBC, CO_L = CO_P + CW_P,
@@ -231,9 +212,6 @@ VIC_DEV void ctx_get_words(const CtxRef& r, size_t word0, T& v, int first, int l
 
 // The residual's inputs, group by group: `cls` = EBG_* bits of the HRU's root find (which groups its evaluations use)
 VIC_DEV int surf_eb_class(const SurfEBConst& c) {
-#ifdef VIC_DEBUG_ALLGROUPS
-  return VIC_DEBUG_ALLGROUPS;
-#endif
   return (c.frozen_on ? EBG_FROZEN : 0) | ((c.snow_coverage > 0 && !c.INCLUDE_SNOW) ? EBG_SNOWCOV : 0) | (c.INCLUDE_SNOW ? EBG_INCL : 0)
          | (!c.SNOWING ? EBG_EVAP : 0) | ((c.VEG && !c.SNOWING) ? EBG_CANOPY : 0);
 }
@@ -912,10 +890,8 @@ struct EArgs {
   int month;
 };
 
-#ifndef VIC_EVAL_WAVES
-#define VIC_EVAL_WAVES 2
-#endif
-__global__ __launch_bounds__(64) VIC_WAVES_PER_EU(VIC_EVAL_WAVES, VIC_EVAL_WAVES) void vic_surf_eval(const EArgs a) {
+constexpr int EVAL_WAVES = 2;
+__global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void vic_surf_eval(const EArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *a.profile_next = 0;
   // Sparse rounds.  A dense launch pays a whole wave -- its chain of dependent loads -- for every 64 HRUs of which one is
   // pending.  The number pending is on the device before the host knows it (the work list the profile kernel has just gone
@@ -998,14 +974,12 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(VIC_EVAL_WAVES, VIC_EVAL_WAVES
   // fluxes are carried from call to call), fallback / error results, QUICK_SOLVE and IMPLICIT (their final evaluation solves
   // another column / is always solved again).
   bool at_root = false;
-#if VIC_FINAL_SHORTCUT
   if (stage_before == SurfSolve::ROOT && sv.stage == SurfSolve::FINAL && !a.implicit && !a.o.QUICK_SOLVE && !(cls & EBG_INCL) && sv.ok
       && sv.fbflag == 0 && sv.Tsurf == x_eval && fabs(fx) < 1.e30) {
     sv.final_slot = slot;
     surf_solve_consume(a.o, sv, eb, eb, fx);       // FINAL -> DONE with this evaluation's residual
     at_root = true;
   }
-#endif
   if (was_quick && sv.stage != SurfSolve::ROOT_QUICK) {
     // QUICK_SOLVE: from here on the whole column is solved; the records of the shortened column are not its solutions.  NOFLUX
     // comes back with a second iteration only (calc_surf_energy_bal.c:403); the final evaluation keeps what was last set
@@ -1317,10 +1291,7 @@ __global__ __launch_bounds__(256) void vic_state_records(const RArgs a) {
 // The host reads the round's list sizes back RB_LAG rounds late (fd_step): it stays that many rounds ahead of the device, so the
 // thin tail rounds -- two short kernels each -- never wait for a host round trip; the price is RB_LAG rounds on empty lists at
 // the end of the iteration (both kernels return at once).
-#ifndef VIC_RB_LAG
-#define VIC_RB_LAG 3
-#endif
-constexpr int RB_LAG = VIC_RB_LAG, RB_DEPTH = RB_LAG + 1;
+constexpr int RB_LAG = 3, RB_DEPTH = RB_LAG + 1;
 struct FdChunk {
   int c0 = 0, ccount = 0;          // cells [c0, c0 + ccount)
   int* d_glist = nullptr;          // their HRUs, ascending
