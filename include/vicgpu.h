@@ -440,10 +440,27 @@ enum {
    * constants the library derives once per domain (cell 0): moist, Wu, layer.  Must equal VICGPU_PURE_SOIL_CONDUCTIVITY
    * fed with that layer's parameters, bit for bit. */
   VICGPU_PURE_SOIL_CONDUCTIVITY_DERIVED = VICGPU_PURE_NFN,
+  /* device-only: the math the frozen-node root finder rests on (vic_math.hpp) */
+  VICGPU_PURE_LN_POS,             /* x */
+  VICGPU_PURE_POW_POS,            /* x, y (with its library fallback outside 0 < x < 1e300) */
+  VICGPU_PURE_POW_POS_APPROX,     /* x, y (y rounded to float as the predictor does) */
+  VICGPU_PURE_RCP_REFINED,        /* d */
   VICGPU_PURE_NFN_DEVICE
 };
 #define VICGPU_PURE_NIN 10
 int   vicgpu_debug_pure(vicgpu_ctx *ctx, int fn, int n, const double *in, double *out);
+
+/* ---- test hook: one Gauss-Seidel visit of one frozen-soil node -----------------
+ * The node's root find of the profile kernels (node_visit, vic_profile.hpp) for n
+ * independent cases, on the record profile_item_store folds from the same inputs.
+ * in: double[n][VICGPU_NODE_NIN] in the reference's terms (soil_thermal_eqn.c):
+ *   A, B, C, D, E, T0, ice0, moist, max_moist, bubble, expt, TL, TU, oldT (the current iterate);
+ * out: double[n][VICGPU_NODE_NOUT]: T, failed (1: the reference's root finder returns ERROR).
+ * mode: an OR of the VICGPU_NODE_* bits, one value for the whole launch. */
+enum { VICGPU_NODE_NODE1 = 1, VICGPU_NODE_NEWTON = 2, VICGPU_NODE_EXP_TRANS = 4 };
+#define VICGPU_NODE_NIN 14
+#define VICGPU_NODE_NOUT 2
+int   vicgpu_debug_node_root(vicgpu_ctx *ctx, int mode, int n, const double *in, double *out);
 
 /* GPU time (ms) per model step of the last vicgpu_step call, measured with
  * hipEvents on the library's streams: QUICK_FLUX: the step's HRU kernel, one

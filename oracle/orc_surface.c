@@ -51,6 +51,35 @@ static double orc_soil_thermal_eqn(double T, void *vctx) {
   return value;
 }
 
+/* test-only: one node visit of orc_solve_T_profile for n independent cases (the device counterpart is vicgpu_debug_node_root).
+ * in: double[n][VICGPU_NODE_NIN] = A, B, C, D, E, T0, ice0, moist, max_moist, bubble, expt, TL, TU, oldT; out: double[n][2] =
+ * T, 1 if the root finder returned ERROR.  A node at or above 0 C takes the closed-form update, a frozen one the root of
+ * orc_soil_thermal_eqn from T0 -+ SOIL_DT with stopping tolerance 2 macheps |T| + ttol (3e-8, 1e-7: the reference's). */
+int vicorc_node_root(const double *in, int n, int node, int EXP_TRANS, double macheps, double ttol, double *out) {
+  int i;
+  if (!in || !out || n < 0) return -1;
+  for (i = 0; i < n; i++) {
+    const double *a = in + (size_t)i * VICGPU_NODE_NIN;
+    orc_ste_ctx c;
+    double T;
+    int err = 0;
+    c.A = a[0]; c.B = a[1]; c.C = a[2]; c.D = a[3]; c.E = a[4]; c.T0 = a[5]; c.ice0 = a[6]; c.moist = a[7];
+    c.max_moist = a[8]; c.bubble = a[9]; c.expt = a[10]; c.TL = a[11]; c.TU = a[12]; c.EXP_TRANS = EXP_TRANS; c.node = node;
+    if (a[13] >= 0) {                                                             /* frozen_soil.c:386-393, 427-436 */
+      if (!EXP_TRANS)
+        T = (c.A * c.T0 + c.B * (c.TL - c.TU) + c.C * c.TL + c.D * c.TU + c.E * (0. - c.ice0)) / (c.A + c.C + c.D);
+      else
+        T = (c.A * c.T0 + c.B * (c.TL - c.TU) + c.C * (c.TL + c.TU) - c.D * (c.TL - c.TU) + c.E * (0. - c.ice0)) / (c.A + 2. * c.C);
+    } else {
+      T = orc_root_brent_tol(c.T0 - (ORC_SOIL_DT), c.T0 + (ORC_SOIL_DT), orc_soil_thermal_eqn, &c, macheps, ttol);
+      err = orc_is_error(T);
+    }
+    out[2 * (size_t)i] = T;
+    out[2 * (size_t)i + 1] = err ? 1.0 : 0.0;
+  }
+  return 0;
+}
+
 /* The per-node freezing parameters calc_soil_thermal_fluxes indexes (frozen_soil.c:397-399).
  * compat: the reference passes the 3-element LAYER arrays max_moist(mm)/bubble/expt, which sit directly in front of
  * the node arrays in soil_con_struct (vicNl_def.h:919-920,932-933,939-940), so index j reads layer[j] for j<3 and

@@ -351,6 +351,19 @@ OracleModel.get_output = _orc_get_output
 OracleModel.set_fluxes = _orc_set_fluxes
 
 
+def oracle_node_root(cases, node, exp_trans, macheps=3e-8, ttol=1e-7):
+    """vicorc_node_root: one node visit of the oracle's solve_T_profile per row of cases [n][VICGPU_NODE_NIN] (the layout of
+    vicgpu_debug_node_root).  Returns (T [n], error [n] bool)."""
+    inp = np.ascontiguousarray(cases, dtype=np.float64)
+    assert inp.ndim == 2 and inp.shape[1] == C["VICGPU_NODE_NIN"]
+    out = np.zeros((inp.shape[0], 2))
+    lib = ctypes.CDLL(oracle_lib_path())
+    f = lib.vicorc_node_root; f.restype = ctypes.c_int
+    f.argtypes = [_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _dp]
+    assert f(_d(inp), inp.shape[0], int(node), int(bool(exp_trans)), float(macheps), float(ttol), _d(out)) == 0
+    return out[:, 0].copy(), out[:, 1] != 0
+
+
 def have_ref(variant="plain"):
     return os.path.exists(ref_lib_path(variant))
 

@@ -31,7 +31,10 @@ SCENARIOS = {
     # with the glacier slot in the top band
     "frozen_cfg3_shape": (dict(FULL_ENERGY=1, FROZEN_SOIL=1, Nnode=10, Nband=5, frozen_compat=0), "fixed", 4, 5, False, 48, 60, 6),
     "frozen_cfg4_shape_glacier": (dict(FULL_ENERGY=1, FROZEN_SOIL=1, Nnode=10, Nband=5, frozen_compat=0), "fixed", 4, 5, True, 48, 60, 6),
+    # soils across the real range (make_domain soils="wide"), from late winter into the thaw
+    "frozen_wide_soils": (dict(FULL_ENERGY=1, FROZEN_SOIL=1, Nnode=10, frozen_compat=0), "fixed", 6, 2, False, 72, 80, 6),
 }
+SOILS = {"frozen_wide_soils": "wide"}     # make_domain's soils draw of a scenario (default: None)
 
 
 def make_pure():
@@ -96,7 +99,7 @@ def main():
         if only and name not in only:
             continue
         opt = abi.default_options(**kw)
-        d = domain.make_domain(ncell, opt, ntile=ntile, glacier_top_band=glacier)
+        d = domain.make_domain(ncell, opt, ntile=ntile, glacier_top_band=glacier, soils=SOILS.get(name))
         f, sf, dmy = domain.make_forcing(d, 0, nsteps, start_doy=doy)
         ref = RefModel(d, variant)
         ref.init_state(f[0], dmy[0], d.init_moist)

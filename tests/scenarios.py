@@ -3,7 +3,8 @@
 SURVEY.md Appendix B), so that no branch is implemented without being pinned oracle-vs-reference AND device-vs-oracle.
 
 Each entry: name -> dict(kw=option overrides, variant=reference build (plain/fixed/compat), ncell, ntile, glacier,
-nsteps (side-by-side run length), doy (start day of year), tweak=optional name of a domain/forcing modifier below).
+nsteps (side-by-side run length), doy (start day of year), tweak=optional name of a domain/forcing modifier below,
+soils=optional make_domain soils draw).
 """
 import numpy as np
 
@@ -57,6 +58,12 @@ OPTION_BRANCHES = {
                             tweak="windy"),
     "blowing_wb_daily": dict(kw=dict(FULL_ENERGY=0, dt=24, snow_step=3, BLOWING=1), variant="plain", ncell=6, ntile=2, nsteps=40, doy=340,
                              tweak="windy"),
+    # soils across the real range (make_domain soils="wide": expt 4-30, bubble 2-80 cm, quartz 0.05-0.9, per layer): the
+    # frozen-node root find on freezing curves the default soils never produce, through the whole step
+    "wide_soils_winter": dict(kw=FROZEN, variant="fixed", ncell=6, ntile=2, nsteps=100, doy=330, soils="wide"),
+    "wide_soils_thaw": dict(kw=FROZEN, variant="fixed", ncell=6, ntile=2, nsteps=120, doy=95, soils="wide"),
+    "wide_soils_exp_trans": dict(kw=dict(FROZEN, EXP_TRANS=1), variant="fixed", ncell=6, ntile=2, nsteps=100, doy=330, soils="wide"),
+    "wide_soils_noflux_n12": dict(kw=dict(FROZEN, NOFLUX=1, Nnode=12), variant="fixed", ncell=6, ntile=2, nsteps=100, doy=10, soils="wide"),
 }
 
 # IMPLICIT soil heat solution (newt_raph_func_fast.c, frozen_soil.c:229-301,540-803): Newton iteration with the explicit
@@ -93,7 +100,7 @@ def build(name, nsteps=None):
     """Domain + forcing of a scenario: returns (spec, d, f, sf, dmy)."""
     sp = OPTION_BRANCHES.get(name) or IMPLICIT_BRANCHES.get(name) or QUICK_SOLVE_BRANCHES.get(name) or RANDOM_COMBINATIONS[name]
     opt = abi.default_options(**sp["kw"])
-    d = domain.make_domain(sp["ncell"], opt, ntile=sp["ntile"], glacier_top_band=sp.get("glacier", False))
+    d = domain.make_domain(sp["ncell"], opt, ntile=sp["ntile"], glacier_top_band=sp.get("glacier", False), soils=sp.get("soils"))
     n = nsteps or sp["nsteps"]
     f, sf, dmy = domain.make_forcing(d, 0, n, start_doy=sp["doy"])
     tw = sp.get("tweak")

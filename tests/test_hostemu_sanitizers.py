@@ -64,3 +64,11 @@ def test_round2_entry_points_clean(hostemu_lib, poison):
     derivation of atmos[rec], and the IMPLICIT profile kernel with its explicit fall-back."""
     out = _run(*hostemu_lib, ["3"], poison, script="check_round2.py")
     assert out.count("worst rel diff") == 5
+
+
+def test_node_root_battery_clean(hostemu_lib):
+    """The frozen-node root battery of tests/test_node_root.py (tests/node_cases.py) through vicgpu_debug_node_root, both
+    node-solver modes, against the arbitrary-precision reference: tools/hostemu/check_node_root.py exits non-zero on any
+    violated bound."""
+    out = _run(*hostemu_lib, [], False, script="check_node_root.py")
+    assert out.count(" 0 violations;") == 2, out

@@ -60,6 +60,7 @@ def load_library():
         "vicgpu_device_ptr": (vp, [vp, ctypes.c_int]),
         "vicgpu_last_kernel_ms": (ctypes.c_int, [vp, _dp, _ip]),
         "vicgpu_debug_pure": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+        "vicgpu_debug_node_root": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
         "vicgpu_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
         "vicgpu_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
@@ -98,7 +99,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_state", "vicgpu_get_state", "vicgpu_push_forcing", "vicgpu_step", "vicgpu_synchronize", "vicgpu_get_fluxes",
     "vicgpu_get_cell_outputs", "vicgpu_get_accum", "vicgpu_reset_accum", "vicgpu_get_cell_errors", "vicgpu_set_stream",
     "vicgpu_set_write_fluxes", "vicgpu_device_ptr", "vicgpu_last_kernel_ms", "vicgpu_debug_pure",
-    "vicgpu_glacier_mass_balance_fit",
+    "vicgpu_debug_node_root", "vicgpu_glacier_mass_balance_fit",
     "vicgpu_out_nvar", "vicgpu_out_var_id", "vicgpu_out_var_name", "vicgpu_out_var_kind", "vicgpu_out_var_agg", "vicgpu_out_var_nelem",
     "vicgpu_put_data_config", "vicgpu_put_data_init", "vicgpu_get_outputs", "vicgpu_get_output_data", "vicgpu_get_balance",
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
@@ -323,6 +324,15 @@ class Model:
         out = np.zeros(inp.shape[0])
         self._chk(self.lib.vicgpu_debug_pure(self.h, int(fn), inp.shape[0], _d(inp), _d(out)))
         return out
+
+    def debug_node_root(self, mode, cases):
+        """Test hook (vicgpu_debug_node_root): one frozen-node visit for every row of cases [n][VICGPU_NODE_NIN];
+        mode: an OR of VICGPU_NODE_NODE1 / _NEWTON / _EXP_TRANS.  Returns (T [n], failed [n] bool)."""
+        inp = np.ascontiguousarray(cases, dtype=np.float64)
+        assert inp.ndim == 2 and inp.shape[1] == C["VICGPU_NODE_NIN"] and inp.shape[0] > 0
+        out = np.zeros((inp.shape[0], C["VICGPU_NODE_NOUT"]))
+        self._chk(self.lib.vicgpu_debug_node_root(self.h, int(mode), inp.shape[0], _d(inp), _d(out)))
+        return out[:, 0].copy(), out[:, 1] != 0
 
     def last_kernel_ms(self):
         ms = ctypes.c_double(0)

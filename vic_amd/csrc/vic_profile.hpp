@@ -171,14 +171,19 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
         const double step = f * x * rcp_refined(den);                     // a step's last digits do not matter (see below)
         double xn = x + step;
         it++;
-        if (fabs(step) <= NODE_NEWTON_TOL) act = false;                      // converged: the step is taken as it is
+        // whether the step stays clear of the kink where the ice content reaches zero (Eu = E moist; Eu is convex in T, so
+        // twice its linear change is an upper bound for small steps).  Next to the kink the curved branch's slope is many
+        // times the ice-free branch's: a small step from the curved side says nothing about the distance to a root past it,
+        // unless the bracket already pins the root (a root at the kink itself).
+        const bool clear = Eu * (1. + 2.2 * fabs(K.Y * step) * rcp_refined(fabs(x))) < K.EM;
+        if (fabs(step) <= NODE_NEWTON_TOL && (!curved || clear || hi - lo <= NODE_NEWTON_TOL)) act = false;   // converged: the
+                                                                                                              // step is taken as it is
         // On the smooth branch of the curve the error left after a Newton step s is |f''/(2 f')| s^2 <= (1 + |Y|) s^2 / (2 |x|)
         // (f' = -S - Y Eu / x, f'' = -Y (Y - 1) Eu / x^2, |x| the smaller end of the step: |s| <= 0.05 |x| keeps it within 5 %,
-        // the bound below has that margin).  When that bound is below the tolerance and the step stays
-        // clear of the kink where the ice content reaches zero (Eu = E moist; Eu is convex in T, so twice its linear change is
-        // an upper bound for small steps), the step is taken without another evaluation to confirm it.
-        else if (curved && fabs(step) <= 0.05 * fabs(x) && (1. + fabs(K.Y)) * step * step <= NODE_NEWTON_ACCEPT * fabs(x)
-                 && Eu * (1. + 2.2 * fabs(K.Y * step) * rcp_refined(fabs(x))) < K.EM) act = false;
+        // the bound below has that margin).  When that bound is below the tolerance and the step stays clear of the kink, the
+        // step is taken without another evaluation to confirm it.
+        else if (curved && fabs(step) <= 0.05 * fabs(x) && (1. + fabs(K.Y)) * step * step <= NODE_NEWTON_ACCEPT * fabs(x) && clear)
+          act = false;
         else {
           // a step that leaves the bracket (a kink of the curve between x and the root) is replaced by a bisection; a step
           // down can only leave it once a lower bound is known

@@ -40,6 +40,24 @@ VIC_DEV double estimate_T1(double Ts, double T1_old, double T2, double D1, doubl
 constexpr int PREC = 11;
 enum { PR_T0 = 0, PR_AT0, PR_B, PR_C, PR_D, PR_EI, PR_S, PR_G, PR_Y, PR_EMOIST, PR_EMM };
 
+// The per-node part of a record (everything but T0): the reference's coefficients A-E of the node and its freezing parameters
+// (max_moist mm, bubble, expt) folded as listed above.  Shared by profile_item_store and the node-root test hook
+// (vicgpu_debug_node_root), so that the hook tests the record the pipeline builds.
+VIC_DEV void profile_node_fold(double* r, bool EXP_TRANS, bool frozen_on, double A, double B, double C, double D, double E,
+                               double T0, double ice0, double moist, double mm, double bub, double ex) {
+  r[PR_S] = !EXP_TRANS ? A + C + D : A + 2. * C;
+  r[PR_AT0] = A * T0;
+  r[PR_B] = B;
+  r[PR_C] = C; r[PR_D] = D;
+  r[PR_EI] = E * (0. - ice0);
+  const double Y = -(2.0 / (ex - 3.0));
+  const double kap = LF / 273.16 / (9.81 * bub / 100.);
+  r[PR_Y] = Y;
+  r[PR_G] = frozen_on ? E * mm * pow_pos(kap, Y) : 0.0;
+  r[PR_EMOIST] = E * moist;
+  r[PR_EMM] = E * mm;
+}
+
 template <int NN>
 VIC_DEV void profile_item_store(const Opt& o, const CellView& cv, const Soil3& s3, const Nodes<NN>& nd, double deltat, bool frozen_on,
                                 double* __restrict__ blk) {
@@ -61,30 +79,19 @@ VIC_DEV void profile_item_store(const Opt& o, const CellView& cv, const Soil3& s
       C = 2 * deltat * nd.kappa[j] * al / ga;
       D = 2 * deltat * nd.kappa[j] * al / be;
       E = ICE_DENSITY * LF * al * al;
-      r[PR_S] = A + C + D;
     } else {
       const double z1 = cv.node(CPN_ZSUM, j) + 1;
       A = 4 * Bexp * Bexp * nd.Cs[j] * z1 * z1;
       C = 4 * deltat * nd.kappa[j];
       D = 2 * deltat * nd.kappa[j] * Bexp;
       E = 4 * Bexp * Bexp * ICE_DENSITY * LF * z1 * z1;
-      r[PR_S] = A + 2. * C;
     }
-    r[PR_AT0] = A * nd.T[j];
-    r[PR_B] = (kup - nd.kappa[j - 1]) * deltat;
-    r[PR_C] = C; r[PR_D] = D;
-    r[PR_EI] = E * (0. - nd.ice[j]);
     double mm, bub, ex;
     if (o.frozen_compat) {
       if (j < 3) { mm = s3.max_moist[j]; bub = cv.lay(CPL_BUBBLE, j); ex = cv.lay(CPL_EXPT, j); }
       else { mm = cv.node(CPN_MAX_MOIST, j - 3); bub = cv.node(CPN_BUBBLE, j - 3); ex = cv.node(CPN_EXPT, j - 3); }
     } else { mm = cv.node(CPN_MAX_MOIST, j); bub = cv.node(CPN_BUBBLE, j); ex = cv.node(CPN_EXPT, j); }
-    const double Y = -(2.0 / (ex - 3.0));
-    const double kap = LF / 273.16 / (9.81 * bub / 100.);
-    r[PR_Y] = Y;
-    r[PR_G] = frozen_on ? E * mm * pow_pos(kap, Y) : 0.0;
-    r[PR_EMOIST] = E * nd.moist[j];
-    r[PR_EMM] = E * mm;
+    profile_node_fold(r, o.EXP_TRANS, frozen_on, A, (kup - nd.kappa[j - 1]) * deltat, C, D, E, nd.T[j], nd.ice[j], nd.moist[j], mm, bub, ex);
   }
 }
 

@@ -1168,9 +1168,34 @@ __global__ __launch_bounds__(64) void vic_debug_pure(const DArgs d) {
       r = soil_conductivity_pre(a[0], a[1], kc);
       break;
     }
+    case VICGPU_PURE_LN_POS: r = ln_pos(a[0]); break;
+    case VICGPU_PURE_POW_POS: r = pow_pos(a[0], a[1]); break;
+    case VICGPU_PURE_POW_POS_APPROX: r = pow_pos_approx(a[0], (float)a[1]); break;
+    case VICGPU_PURE_RCP_REFINED: r = rcp_refined(a[0]); break;
     default: break;
   }
   d.out[i] = r;
+}
+
+// One node visit per lane (vicgpu_debug_node_root).  Every lane of every wave calls node_visit, which votes across the
+// wave: lanes past the last case take part with sweeping = false.
+struct NRArgs { int n; bool EXP_TRANS; const double* in; double* out; };
+
+template <bool NODE1, bool NEWTON>
+__global__ __launch_bounds__(64) void vic_debug_node_root(const NRArgs d) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const bool live = i < d.n;
+  const double* a = d.in + (size_t)(live ? i : 0) * VICGPU_NODE_NIN;
+  double rec[PREC];
+  profile_node_fold(rec, d.EXP_TRANS, true, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10]);
+  NodeK K;
+  K.load(rec);
+  bool failed;
+  const double T = node_visit<NODE1, NEWTON>(live, true, d.EXP_TRANS, K, a[13], a[11], a[12], a[5], failed);
+  if (live) {
+    d.out[(size_t)i * VICGPU_NODE_NOUT] = T;
+    d.out[(size_t)i * VICGPU_NODE_NOUT + 1] = failed ? 1.0 : 0.0;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ cell kernel
@@ -2262,6 +2287,30 @@ int vicgpu_debug_pure(vicgpu_ctx* c, int fn, int n, const double* in, double* ou
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
+  HIPIGN(hipFree(d_in)); HIPIGN(hipFree(d_out));
+  HIPCHK(c, e);
+  return VICGPU_OK;
+}
+
+int vicgpu_debug_node_root(vicgpu_ctx* c, int mode, int n, const double* in, double* out) {
+  if (!c || mode < 0 || mode > (VICGPU_NODE_NODE1 | VICGPU_NODE_NEWTON | VICGPU_NODE_EXP_TRANS) || n <= 0 || !in || !out) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  double *d_in = nullptr, *d_out = nullptr;
+  HIPCHK(c, hipMalloc(&d_in, sizeof(double) * (size_t)n * VICGPU_NODE_NIN));
+  HIPCHK(c, hipMalloc(&d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT));
+  HIPCHK(c, copy_on(c->stream, d_in, in, sizeof(double) * (size_t)n * VICGPU_NODE_NIN, hipMemcpyHostToDevice));
+  NRArgs d;
+  d.n = n; d.EXP_TRANS = (mode & VICGPU_NODE_EXP_TRANS) != 0; d.in = d_in; d.out = d_out;
+  const dim3 grid((n + 63) / 64), block(64);
+  switch (mode & (VICGPU_NODE_NODE1 | VICGPU_NODE_NEWTON)) {
+    case 0: hipLaunchKernelGGL((vic_debug_node_root<false, false>), grid, block, 0, c->stream, d); break;
+    case VICGPU_NODE_NODE1: hipLaunchKernelGGL((vic_debug_node_root<true, false>), grid, block, 0, c->stream, d); break;
+    case VICGPU_NODE_NEWTON: hipLaunchKernelGGL((vic_debug_node_root<false, true>), grid, block, 0, c->stream, d); break;
+    default: hipLaunchKernelGGL((vic_debug_node_root<true, true>), grid, block, 0, c->stream, d); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT, hipMemcpyDeviceToHost);
   HIPIGN(hipFree(d_in)); HIPIGN(hipFree(d_out));
   HIPCHK(c, e);
   return VICGPU_OK;

@@ -224,7 +224,7 @@ class Domain:
 
 
 def make_domain(ncell, opt, ntile=1, tile_classes=None, glacier_top_band=False, seed=SEED, band_spread=400.0, bare_fraction=0.0,
-                cell_range=None):
+                cell_range=None, soils=None):
     """Regular grid of `ncell` cells, opt.Nband snow bands x ntile veg tiles per band.
 
     HRU numbering is slot-major: hru = slot * ncell + cell with slot = tile * Nband + band, so a
@@ -280,6 +280,16 @@ def make_domain(ncell, opt, ntile=1, tile_classes=None, glacier_top_band=False, 
     Ksat = np.tile(u_ksat, (3, 1))
     bubble = 0.32 * expt + 4.3
     quartz = np.tile(u_quartz, (3, 1))
+    if soils == "wide":
+        # soils across the range of real soil files, drawn per cell and per layer, independently: the freezing curve's
+        # exponent -2/(expt-3) and air-entry pressure, node averaging across differing layers (node_parameters), the quartz
+        # < 0.2 branch of the conductivity.  Own generator: the default draws above, and every fixture built on them, stay.
+        rng_w = np.random.default_rng([seed, 0x5011])
+        expt = rng_w.uniform(4.0, 30.0, (3, ng))[:, sl]
+        bubble = rng_w.uniform(2.0, 80.0, (3, ng))[:, sl]
+        quartz = rng_w.uniform(0.05, 0.9, (3, ng))[:, sl]
+    elif soils is not None:
+        raise ValueError("soils: None or 'wide'")
     bulk = np.tile(u_bulk, (3, 1))
     soil_dens = np.full((3, ncell), 2650.0)
     organic = np.zeros((3, ncell))
