@@ -1,0 +1,84 @@
+/*
+ * vicgpu_group.h — several GPUs driven from one process: a device group.
+ *
+ * The reference's driver is one process (vicNl.c:506-610: the loop over cells, then write_data_all_cells).  A single
+ * context (vicgpu.h) drives one device.  A group owns N shard contexts of ONE domain and takes and returns every table in
+ * the caller's global layout, so a driver written against a single context changes only the handle type:
+ *
+ *     vicgpu_ctx *c;   vicgpu_create(&opt, 0, &c);          vicgpu_set_domain(c, ...);   vicgpu_step(c, 0, n);
+ *     vicgpu_group *g; vicgpu_group_create(&opt, 8, 0, &g); vicgpu_group_set_domain(g, ...); vicgpu_group_step(g, 0, n);
+ *
+ * Shards.  vicgpu_group_set_domain cuts the domain into nshard contiguous cell blocks [b[k], b[k+1]) of near-equal HRU count
+ * (vicgpu_group_partition, the same rule as vic_amd/shard.py partition_cells).  Shard k holds those cells and their HRUs in
+ * the domain's HRU order restricted to the block, renumbered from 0; its cell_hru_list is the block's part of the caller's,
+ * renumbered the same way.  Every shard must get at least one cell.
+ *
+ * Tables.  Per-HRU tables (state, fluxes: [nrow][nhru]) are in the caller's HRU numbering and are split / merged on the host.
+ * Per-cell tables (forcing, raw forcing, output floats, balance, cell error flags, glacier fit) are the caller's
+ * [..][ncell] tables: each shard's columns go to and from the caller's buffer by pitched copies, directly from and into
+ * pinned memory (vicgpu_host_alloc).  State records ([nhru][VICGPU_SR_LEN], cell-major hruList order) are the shards'
+ * record streams concatenated in shard order.
+ *
+ * Threads.  The group has one persistent host thread per shard; each entry runs the shards' calls on them at the same
+ * time and returns when all have returned.  A finite-difference vicgpu_step blocks for most of the run time, so the shards
+ * only overlap because of these threads.  With QUICK_FLUX vicgpu_group_step only enqueues; vicgpu_group_synchronize waits.
+ * Like a context, a group is not thread-safe: one caller thread at a time.
+ *
+ * Errors.  The codes of vicgpu.h.  When a shard fails, the entry returns the first failing shard's code and
+ * vicgpu_group_last_error reads "shard k (device d): <the context's message>".
+ */
+#ifndef VICGPU_GROUP_H_
+#define VICGPU_GROUP_H_
+
+#include "vicgpu.h"
+#include "vicgpu_out.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct vicgpu_group vicgpu_group;
+
+/* The shard boundaries bounds[nshard+1] of a domain given by its CSR offsets cell_hru_offset[ncell+1]: bounds[0] = 0,
+ * bounds[nshard] = ncell and, for 0 < r < nshard, the first cell c with cell_hru_offset[c] >= nhru * r / nshard, clamped to
+ * [bounds[r-1], ncell].  Pure host function, no device needed.  VICGPU_ERR_ARG for nshard < 1 or nshard > ncell. */
+int  vicgpu_group_partition(int ncell, const int *cell_hru_offset, int nshard, int *bounds);
+
+/* nshard contexts with the same options; devices[nshard] may repeat an index (several shards on one device), NULL means
+ * 0 .. nshard-1.  A device index outside hipGetDeviceCount is VICGPU_ERR_ARG; options vicgpu_create refuses are refused
+ * with its code.  On failure nothing is left behind (*out = NULL). */
+int  vicgpu_group_create(const vicgpu_options *opt, int nshard, const int *devices, vicgpu_group **out);
+void vicgpu_group_destroy(vicgpu_group *g);
+const char *vicgpu_group_last_error(const vicgpu_group *g);
+int  vicgpu_group_shard_bounds(vicgpu_group *g, int *bounds);          /* [nshard+1], after vicgpu_group_set_domain */
+vicgpu_ctx *vicgpu_group_shard_ctx(vicgpu_group *g, int k);           /* shard k's context (tuning, debug and stream entries) */
+
+/* the entries of vicgpu.h / vicgpu_out.h on the whole domain, tables in the caller's global layout */
+int vicgpu_group_set_veglib(vicgpu_group *g, int nrow, const double *veglib);
+int vicgpu_group_set_domain(vicgpu_group *g, int ncell, int nhru, const double *cell_params, const int *hru_iparams,
+                            const double *hru_dparams, const int *cell_hru_offset, const int *cell_hru_list);
+int vicgpu_group_set_state(vicgpu_group *g, const double *state_d, const int *state_i);
+int vicgpu_group_get_state(vicgpu_group *g, double *state_d, int *state_i);
+int vicgpu_group_set_fluxes(vicgpu_group *g, const double *flux);
+int vicgpu_group_get_fluxes(vicgpu_group *g, double *flux);
+int vicgpu_group_push_forcing(vicgpu_group *g, int nsteps, const double *forcing, const unsigned char *snowflag, const int *dmy);
+int vicgpu_group_prefetch_forcing(vicgpu_group *g, int nsteps, const double *forcing, const unsigned char *snowflag,
+                                  const int *dmy);
+int vicgpu_group_prefetch_forcing_raw(vicgpu_group *g, int nsteps, const double *raw, const int *dmy, double min_wind_speed,
+                                      int plapse);
+int vicgpu_group_swap_forcing(vicgpu_group *g);
+int vicgpu_group_step(vicgpu_group *g, int step0, int nsteps);
+int vicgpu_group_synchronize(vicgpu_group *g);
+int vicgpu_group_put_data_config(vicgpu_group *g, int out_step_ratio);
+int vicgpu_group_put_data_init(vicgpu_group *g);
+int vicgpu_group_get_outputs(vicgpu_group *g, int nvar, const int *var_ids, float *out, int reset);
+int vicgpu_group_get_balance(vicgpu_group *g, double *pb);
+int vicgpu_group_get_cell_errors(vicgpu_group *g, int *flags);
+int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
+int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
+int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* VICGPU_GROUP_H_ */

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <ucontext.h>
@@ -42,7 +43,8 @@ inline dim3 blockDim, gridDim;
 
 typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorInvalidValue = 1 };
-typedef struct hostemu_stream* hipStream_t;
+struct hostemu_stream { char token; };
+typedef hostemu_stream* hipStream_t;
 struct hostemu_event { std::chrono::steady_clock::time_point t; };
 typedef hostemu_event* hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
@@ -183,8 +185,36 @@ inline void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
       }
 }
 
+// runtime objects alive (device and pinned allocations, streams, events): a failed call that leaves one behind shows up here
+inline std::atomic<long long> live_objects{0};
+
+// pinned host memory (hipHostMalloc) is told apart from pageable memory like the runtime does it, by address range
+struct PinnedMap {
+  std::mutex m;
+  std::map<uintptr_t, size_t> range;           // start -> bytes
+};
+inline PinnedMap& pinned() { static PinnedMap* p = new PinnedMap; return *p; }
+inline void* pinned_alloc(size_t n) {
+  void* p = malloc(n ? n : 1);
+  if (p) { std::lock_guard<std::mutex> lk(pinned().m); pinned().range[(uintptr_t)p] = n ? n : 1; live_objects++; }
+  return p;
+}
+inline void pinned_free(void* p) {
+  if (!p) return;
+  { std::lock_guard<std::mutex> lk(pinned().m); pinned().range.erase((uintptr_t)p); live_objects--; }
+  free(p);
+}
+inline bool is_pinned(const void* q) {
+  std::lock_guard<std::mutex> lk(pinned().m);
+  auto it = pinned().range.upper_bound((uintptr_t)q);
+  if (it == pinned().range.begin()) return false;
+  --it;
+  return (uintptr_t)q < it->first + it->second;
+}
+
 inline void* device_alloc(size_t n) {
   void* p = malloc(n ? n : 1);
+  if (p) live_objects++;
   static const bool poison = getenv("HOSTEMU_POISON") && atoi(getenv("HOSTEMU_POISON"));
   if (p && poison) memset(p, 0xFF, n);           // doubles: NaN; ints: -1
   return p;
@@ -218,11 +248,16 @@ inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 2; return hipSuccess; }
 template <typename K> inline hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, K, int, size_t) { *n = 1; return hipSuccess; }
 template <typename T> inline hipError_t hipMalloc(T** p, size_t n) { *p = (T*)hostemu::device_alloc(n); return *p ? hipSuccess : hipErrorInvalidValue; }
-template <typename T> inline hipError_t hipHostMalloc(T** p, size_t n, unsigned = 0) { *p = (T*)malloc(n ? n : 1); return *p ? hipSuccess : hipErrorInvalidValue; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+template <typename T> inline hipError_t hipHostMalloc(T** p, size_t n, unsigned = 0) { *p = (T*)hostemu::pinned_alloc(n); return *p ? hipSuccess : hipErrorInvalidValue; }
+inline hipError_t hipFree(void* p) { if (p) hostemu::live_objects--; free(p); return hipSuccess; }
+inline hipError_t hipHostFree(void* p) { hostemu::pinned_free(p); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { memcpy(d, s, n); return hipSuccess; }
+inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind,
+                                   hipStream_t = nullptr) {
+  for (size_t r = 0; r < height; r++) memcpy((char*)d + r * dpitch, (const char*)s + r * spitch, width);
+  return hipSuccess;
+}
 inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { memset(d, v, n); return hipSuccess; }
 inline hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t width, size_t height, hipStream_t = nullptr) {
@@ -231,19 +266,25 @@ inline hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t width, s
 }
 inline hipError_t hipMemcpyFromSymbol(void* d, const void* sym, size_t n) { memcpy(d, sym, n); return hipSuccess; }
 inline hipError_t hipMemcpyToSymbol(void* sym, const void* s, size_t n) { memcpy(sym, s, n); return hipSuccess; }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return hipSuccess; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new hostemu_stream; hostemu::live_objects++; return hipSuccess; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) hostemu::live_objects--; delete s; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hostemu_event; return hipSuccess; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hostemu_event; return hipSuccess; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hostemu_event; hostemu::live_objects++; return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hostemu_event; hostemu::live_objects++; return hipSuccess; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hostemu::live_objects--; delete e; return hipSuccess; }
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t = nullptr) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 enum hipMemoryType { hipMemoryTypeUnregistered = 0, hipMemoryTypeHost = 1, hipMemoryTypeDevice = 2 };
 struct hipPointerAttribute_t { hipMemoryType type; };
-inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) { a->type = hipMemoryTypeUnregistered; return hipSuccess; }
+inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
+  a->type = hostemu::is_pinned(p) ? hipMemoryTypeHost : hipMemoryTypeUnregistered;
+  return hipSuccess;
+}
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
   *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
   return hipSuccess;
 }
+
+// checker hook (tools/hostemu/check_group.py): the number of runtime objects alive
+extern "C" __attribute__((visibility("default"))) long long hostemu_live_objects(void) { return hostemu::live_objects.load(); }

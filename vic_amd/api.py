@@ -3,8 +3,10 @@
 The method names mirror the reference driver's vocabulary for this path
 (vicNl.c:390-654 runModel / dist_prec.c:8 dist_prec): a `Model` owns the domain
 tables on one GPU, `push_forcing` replaces cell.atmos[rec], `dist_prec(rec0, n)`
-advances every cell n records.  There is NO CPU fallback: if the HIP library is
-missing or no GPU is visible, construction raises.
+advances every cell n records.  A `Group` (include/vicgpu_group.h) is the same
+on several contexts at once: one domain cut into contiguous cell blocks, one
+block per device, tables in the domain's global layout.  There is NO CPU
+fallback: if the HIP library is missing or no GPU is visible, construction raises.
 """
 import ctypes
 import os
@@ -83,6 +85,33 @@ def load_library():
         "vicgpu_get_output_data": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _dp]),
         "vicgpu_get_balance": (ctypes.c_int, [vp, _dp]),
         "vicgpu_set_fluxes": (ctypes.c_int, [vp, _dp]),
+        # include/vicgpu_group.h
+        "vicgpu_group_partition": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, _ip]),
+        "vicgpu_group_create": (ctypes.c_int, [ctypes.POINTER(abi.Options), ctypes.c_int, _ip, ctypes.POINTER(vp)]),
+        "vicgpu_group_destroy": (None, [vp]),
+        "vicgpu_group_last_error": (ctypes.c_char_p, [vp]),
+        "vicgpu_group_shard_bounds": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_group_shard_ctx": (vp, [vp, ctypes.c_int]),
+        "vicgpu_group_set_veglib": (ctypes.c_int, [vp, ctypes.c_int, _dp]),
+        "vicgpu_group_set_domain": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _ip, _dp, _ip, _ip]),
+        "vicgpu_group_set_state": (ctypes.c_int, [vp, _dp, _ip]),
+        "vicgpu_group_get_state": (ctypes.c_int, [vp, _dp, _ip]),
+        "vicgpu_group_set_fluxes": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_get_fluxes": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_push_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
+        "vicgpu_group_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
+        "vicgpu_group_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
+        "vicgpu_group_swap_forcing": (ctypes.c_int, [vp]),
+        "vicgpu_group_step": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        "vicgpu_group_synchronize": (ctypes.c_int, [vp]),
+        "vicgpu_group_put_data_config": (ctypes.c_int, [vp, ctypes.c_int]),
+        "vicgpu_group_put_data_init": (ctypes.c_int, [vp]),
+        "vicgpu_group_get_outputs": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),
+        "vicgpu_group_get_balance": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_get_cell_errors": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_group_get_state_records": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_set_state_records": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -93,6 +122,13 @@ def load_library():
     _lib = lib
     return lib
 
+
+# the entries of include/vicgpu_group.h that mirror a single-context entry: vicgpu_group_<name> for vicgpu_<name>
+GROUP_ENTRIES = [
+    "destroy", "last_error", "set_veglib", "set_domain", "set_state", "get_state", "set_fluxes", "get_fluxes", "push_forcing",
+    "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
+    "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
+]
 
 EXPORTED_SYMBOLS = [
     "vicgpu_abi_version", "vicgpu_create", "vicgpu_destroy", "vicgpu_last_error", "vicgpu_set_veglib", "vicgpu_set_domain",
@@ -105,7 +141,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free",
-]
+] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
 def _d(a):
@@ -339,3 +375,64 @@ class Model:
         n = ctypes.c_int(0)
         self._chk(self.lib.vicgpu_last_kernel_ms(self.h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
+
+
+def partition(cell_hru_offset, nshard):
+    """vicgpu_group_partition: the shard boundaries [nshard+1] the group cuts a domain at (the rule of shard.partition_cells)."""
+    lib = load_library()
+    off = np.ascontiguousarray(cell_hru_offset, dtype=np.int32)
+    b = np.zeros(int(nshard) + 1, dtype=np.int32)
+    rc = lib.vicgpu_group_partition(len(off) - 1, _i(off), int(nshard), _i(b))
+    if rc != 0:
+        raise VicGpuError("vicgpu_group_partition failed with code %d" % rc)
+    return b
+
+
+class _GroupLib:
+    """The library as a Group's methods see it: vicgpu_<name> is vicgpu_group_<name> for every entry the group mirrors, the
+    functions that take no context (vicgpu_out_*, vicgpu_host_*) are the library's own, anything else has no group form."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        base = name[len("vicgpu_"):]
+        if base in GROUP_ENTRIES:
+            return getattr(self._lib, "vicgpu_group_" + base)
+        if base.startswith(("out_", "host_", "group_")):
+            return getattr(self._lib, name)
+        raise AttributeError("%s has no device-group form (use Group.shard_ctx)" % name)
+
+
+class Group(Model):
+    """One domain on several contexts (include/vicgpu_group.h): contiguous cell blocks, one per entry of `devices` (devices
+    may repeat), stepped at the same time from one host thread per shard.  Model's methods, on the whole domain: every
+    table goes in and comes out in the domain's global layout."""
+
+    def __init__(self, dom, devices=(0,)):
+        lib = load_library()
+        self.lib = _GroupLib(lib)
+        self.dom = dom
+        self.opt = dom.opt
+        self.devices = np.ascontiguousarray(devices, dtype=np.int32)
+        h = ctypes.c_void_p()
+        rc = lib.vicgpu_group_create(ctypes.byref(dom.opt), len(self.devices), _i(self.devices), ctypes.byref(h))
+        if rc != 0:
+            raise VicGpuError("vicgpu_group_create failed with code %d (no GPU, a device out of range, or unsupported options)" % rc)
+        self.h = h
+        self._chk(self.lib.vicgpu_set_veglib(h, dom.veglib.shape[0], _d(np.ascontiguousarray(dom.veglib))))
+        self._chk(self.lib.vicgpu_set_domain(h, dom.ncell, dom.nhru, _d(dom.cell_params), _i(dom.hru_iparams),
+                                             _d(dom.hru_dparams), _i(dom.cell_hru_offset), _i(dom.cell_hru_list)))
+
+    def shard_bounds(self):
+        """[nshard+1]: shard k holds the cells [b[k], b[k+1])."""
+        b = np.zeros(len(self.devices) + 1, dtype=np.int32)
+        self._chk(self.lib.vicgpu_group_shard_bounds(self.h, _i(b)))
+        return b
+
+    def shard_ctx(self, k):
+        """Shard k's vicgpu_ctx handle, for the per-context entries (stream, tuning, debug)."""
+        p = self.lib.vicgpu_group_shard_ctx(self.h, int(k))
+        if not p:
+            raise VicGpuError("no shard %d" % k)
+        return ctypes.c_void_p(p)

@@ -1,0 +1,407 @@
+// vic_group.hpp — the device group of include/vicgpu_group.h: N shard contexts of one domain, stepped at the same time.
+//
+// Host code only, included at the end of vicgpu_api.hip: it builds on the single-context entries and on their pitched
+// variants (prefetch_impl, get_outputs_impl, glacier_fit_impl, d2h_cols), which copy one shard's columns straight between
+// the device and the caller's global [..][ncell] table.  No kernel lives here.
+#pragma once
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include "vicgpu_group.h"
+
+// One persistent host thread per shard.  run(fn) calls fn(k) on thread k for every shard and returns when all have returned.
+// Each thread selects its shard's device once at start (every library entry selects it again anyway).
+class ShardThreads {
+ public:
+  void start(const std::vector<int>& devices) {
+    for (size_t k = 0; k < devices.size(); k++) th_.emplace_back([this, k, d = devices[k]]() { loop((int)k, d); });
+  }
+  void run(const std::function<void(int)>& fn) {
+    std::unique_lock<std::mutex> lk(m_);
+    job_ = &fn;
+    pending_ = (int)th_.size();
+    gen_++;
+    go_.notify_all();
+    done_.wait(lk, [this]() { return pending_ == 0; });
+    job_ = nullptr;
+  }
+  void stop() {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      quit_ = true;
+    }
+    go_.notify_all();
+    for (std::thread& t : th_) t.join();
+    th_.clear();
+  }
+
+ private:
+  void loop(int k, int device) {
+    HIPIGN(hipSetDevice(device));
+    unsigned long long seen = 0;
+    for (;;) {
+      const std::function<void(int)>* fn;
+      {
+        std::unique_lock<std::mutex> lk(m_);
+        go_.wait(lk, [&]() { return quit_ || gen_ != seen; });
+        if (quit_) return;
+        seen = gen_;
+        fn = job_;
+      }
+      (*fn)(k);
+      std::lock_guard<std::mutex> lk(m_);
+      if (--pending_ == 0) done_.notify_one();
+    }
+  }
+  std::vector<std::thread> th_;
+  std::mutex m_;
+  std::condition_variable go_, done_;
+  const std::function<void(int)>* job_ = nullptr;
+  unsigned long long gen_ = 0;
+  int pending_ = 0;
+  bool quit_ = false;
+};
+
+struct vicgpu_group {
+  vicgpu_options opt;
+  std::vector<int> device;
+  std::vector<vicgpu_ctx*> ctx;
+  ShardThreads threads;
+  std::string err;
+  bool domain_ready = false;
+  int ncell = 0, nhru = 0;
+  std::vector<int> bounds;                  // [nshard+1]: shard k holds the cells [bounds[k], bounds[k+1])
+  std::vector<std::vector<int>> hru;        // shard k's HRUs: global id of its HRU j
+  std::vector<int> rec_first;               // [nshard]: index of shard k's first state record = cell_hru_offset[bounds[k]]
+  std::vector<int> rec_band, rec_veg;       // band and vegetation class of every state record (cell-major hruList order)
+  int nshard() const { return (int)ctx.size(); }
+  int c0(int k) const { return bounds[k]; }
+};
+
+// fn(k) -> status on every shard at the same time; the first failing shard's code and message
+static int group_each(vicgpu_group* g, const std::function<int(int)>& fn) {
+  std::vector<int> rc(g->nshard(), VICGPU_OK);
+  g->threads.run([&](int k) { rc[k] = fn(k); });
+  for (int k = 0; k < g->nshard(); k++)
+    if (rc[k] != VICGPU_OK) {
+      g->err = "shard " + std::to_string(k) + " (device " + std::to_string(g->device[k]) + "): " + vicgpu_last_error(g->ctx[k]);
+      return rc[k];
+    }
+  return VICGPU_OK;
+}
+
+static int group_fail(vicgpu_group* g, int code, const std::string& msg) {
+  g->err = msg;
+  return code;
+}
+
+// The per-HRU table [nrow][nhru] of the caller <-> shard k's [nrow][nhru_k] (its HRUs in its own numbering)
+template <typename T>
+static void split_hru_table(const vicgpu_group* g, int k, const T* global, int nrow, std::vector<T>& local) {
+  const std::vector<int>& ids = g->hru[k];
+  const size_t n = ids.size();
+  local.resize((size_t)nrow * n);
+  for (int r = 0; r < nrow; r++) {
+    const T* src = global + (size_t)r * g->nhru;
+    T* dst = local.data() + (size_t)r * n;
+    for (size_t j = 0; j < n; j++) dst[j] = src[ids[j]];
+  }
+}
+template <typename T>
+static void merge_hru_table(const vicgpu_group* g, int k, const std::vector<T>& local, int nrow, T* global) {
+  const std::vector<int>& ids = g->hru[k];
+  const size_t n = ids.size();
+  for (int r = 0; r < nrow; r++) {
+    const T* src = local.data() + (size_t)r * n;
+    T* dst = global + (size_t)r * g->nhru;
+    for (size_t j = 0; j < n; j++) dst[ids[j]] = src[j];
+  }
+}
+
+static bool group_ready(vicgpu_group* g) {
+  if (g->domain_ready) return true;
+  g->err = "no domain: call vicgpu_group_set_domain first";
+  return false;
+}
+
+extern "C" {
+
+int vicgpu_group_partition(int ncell, const int* off, int nshard, int* bounds) {
+  if (ncell < 1 || !off || !bounds || nshard < 1 || nshard > ncell || off[0] != 0) return VICGPU_ERR_ARG;
+  for (int i = 0; i < ncell; i++)
+    if (off[i + 1] < off[i]) return VICGPU_ERR_ARG;
+  const long long nhru = off[ncell];
+  bounds[0] = 0;
+  for (int r = 1; r < nshard; r++) {
+    const double target = (double)(nhru * r) / nshard;                 // vic_amd/shard.py partition_cells
+    const int c = (int)(std::lower_bound(off, off + ncell + 1, target, [](int a, double t) { return (double)a < t; }) - off);
+    bounds[r] = std::min(std::max(c, bounds[r - 1]), ncell);
+  }
+  bounds[nshard] = ncell;
+  return VICGPU_OK;
+}
+
+void vicgpu_group_destroy(vicgpu_group* g) {
+  if (!g) return;
+  g->threads.stop();
+  for (vicgpu_ctx* c : g->ctx) vicgpu_destroy(c);
+  delete g;
+}
+
+int vicgpu_group_create(const vicgpu_options* opt, int nshard, const int* devices, vicgpu_group** out) {
+  if (!opt || !out || nshard < 1) return VICGPU_ERR_ARG;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VICGPU_ERR_HIP;   // no CPU fallback, like vicgpu_create
+  std::vector<int> dev(nshard);
+  for (int k = 0; k < nshard; k++) {
+    dev[k] = devices ? devices[k] : k;
+    if (dev[k] < 0 || dev[k] >= ndev) return VICGPU_ERR_ARG;
+  }
+  vicgpu_group* g = new vicgpu_group();
+  g->opt = *opt;
+  g->device = dev;
+  for (int k = 0; k < nshard; k++) {
+    vicgpu_ctx* c = nullptr;
+    const int r = vicgpu_create(opt, dev[k], &c);
+    if (r != VICGPU_OK) {
+      vicgpu_group_destroy(g);                    // no thread started yet: destroys the contexts made so far
+      return r;
+    }
+    g->ctx.push_back(c);
+  }
+  try {
+    g->threads.start(dev);
+  } catch (...) {                                 // std::system_error: no thread could be started
+    vicgpu_group_destroy(g);                      // joins the threads that did start
+    return VICGPU_ERR_NOMEM;
+  }
+  *out = g;
+  return VICGPU_OK;
+}
+
+const char* vicgpu_group_last_error(const vicgpu_group* g) { return g ? g->err.c_str() : "null group"; }
+
+int vicgpu_group_shard_bounds(vicgpu_group* g, int* bounds) {
+  if (!g || !bounds) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  std::copy(g->bounds.begin(), g->bounds.end(), bounds);
+  return VICGPU_OK;
+}
+
+vicgpu_ctx* vicgpu_group_shard_ctx(vicgpu_group* g, int k) { return (g && k >= 0 && k < g->nshard()) ? g->ctx[k] : nullptr; }
+
+int vicgpu_group_set_veglib(vicgpu_group* g, int nrow, const double* veglib) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_set_veglib(g->ctx[k], nrow, veglib); });
+}
+
+int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* cp, const int* hpi, const double* hpd, const int* off,
+                            const int* list) {
+  if (!g) return VICGPU_ERR_ARG;
+  g->domain_ready = false;
+  if (ncell <= 0 || nhru <= 0 || !cp || !hpi || !hpd || !off || !list) return group_fail(g, VICGPU_ERR_ARG, "set_domain: bad arguments");
+  // the checks of vicgpu_set_domain on the whole domain: every index used below to slice it is valid after them
+  if (off[0] != 0 || off[ncell] != nhru) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset does not span the HRUs");
+  std::vector<char> seen(nhru, 0);
+  for (int i = 0; i < ncell; i++) {
+    if (off[i + 1] < off[i]) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset decreases");
+    for (int j = off[i]; j < off[i + 1]; j++) {
+      const int h = list[j];
+      if (h < 0 || h >= nhru || seen[h] || hpi[(size_t)HPI_CELL * nhru + h] != i)
+        return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_list entry " + std::to_string(j) + " does not match the domain");
+      seen[h] = 1;
+    }
+  }
+  const int ns = g->nshard();
+  std::vector<int> b(ns + 1);
+  if (vicgpu_group_partition(ncell, off, ns, b.data()) != VICGPU_OK)
+    return group_fail(g, VICGPU_ERR_ARG, "set_domain: " + std::to_string(ns) + " shards for " + std::to_string(ncell) + " cells");
+  for (int k = 0; k < ns; k++)
+    if (b[k + 1] == b[k]) return group_fail(g, VICGPU_ERR_ARG, "set_domain: shard " + std::to_string(k) + " gets no cell");
+  // shard k: its cells' HRUs in the domain's HRU order, renumbered from 0 (vic_amd/shard.py shard_domain)
+  g->hru.assign(ns, std::vector<int>());
+  std::vector<int> shard_of(ncell), new_id(nhru);
+  for (int k = 0; k < ns; k++)
+    for (int i = b[k]; i < b[k + 1]; i++) shard_of[i] = k;
+  for (int h = 0; h < nhru; h++) {
+    std::vector<int>& ids = g->hru[shard_of[hpi[(size_t)HPI_CELL * nhru + h]]];
+    new_id[h] = (int)ids.size();
+    ids.push_back(h);
+  }
+  g->ncell = ncell; g->nhru = nhru; g->bounds = b;
+  const int cp_nrow = VICGPU_CP_NROW(g->opt.Nnode, g->opt.Nband);
+  const int r = group_each(g, [&](int k) {
+    const int c0 = b[k], nc = b[k + 1] - b[k];
+    const std::vector<int>& ids = g->hru[k];
+    const int nh = (int)ids.size();
+    std::vector<double> cpk((size_t)cp_nrow * nc), hpdk;
+    for (int row = 0; row < cp_nrow; row++)
+      std::copy(cp + (size_t)row * ncell + c0, cp + (size_t)row * ncell + c0 + nc, cpk.begin() + (size_t)row * nc);
+    std::vector<int> hpik;
+    split_hru_table(g, k, hpi, HPI_NROW, hpik);
+    for (int j = 0; j < nh; j++) hpik[(size_t)HPI_CELL * nh + j] -= c0;
+    split_hru_table(g, k, hpd, HPD_NROW, hpdk);
+    std::vector<int> offk(nc + 1), listk(off[c0 + nc] - off[c0]);
+    for (int i = 0; i <= nc; i++) offk[i] = off[c0 + i] - off[c0];
+    for (size_t j = 0; j < listk.size(); j++) listk[j] = new_id[list[off[c0] + j]];
+    return vicgpu_set_domain(g->ctx[k], nc, nh, cpk.data(), hpik.data(), hpdk.data(), offk.data(), listk.data());
+  });
+  if (r != VICGPU_OK) return r;
+  g->rec_band.resize(nhru); g->rec_veg.resize(nhru);
+  for (int j = 0; j < nhru; j++) {
+    g->rec_band[j] = hpi[(size_t)HPI_BAND * nhru + list[j]];
+    g->rec_veg[j] = hpi[(size_t)HPI_VEG_CLASS * nhru + list[j]];
+  }
+  g->rec_first.resize(ns);
+  for (int k = 0; k < ns; k++) g->rec_first[k] = off[b[k]];
+  g->domain_ready = true;
+  return VICGPU_OK;
+}
+
+int vicgpu_group_set_state(vicgpu_group* g, const double* sd, const int* si) {
+  if (!g || !sd || !si) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    std::vector<double> d;
+    std::vector<int> i;
+    split_hru_table(g, k, sd, VICGPU_SD_NROW(g->opt.Nnode), d);
+    split_hru_table(g, k, si, VICGPU_SI_NROW(g->opt.Nnode), i);
+    return vicgpu_set_state(g->ctx[k], d.data(), i.data());
+  });
+}
+
+int vicgpu_group_get_state(vicgpu_group* g, double* sd, int* si) {
+  if (!g || !sd || !si) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    const size_t n = g->hru[k].size();
+    std::vector<double> d((size_t)VICGPU_SD_NROW(g->opt.Nnode) * n);
+    std::vector<int> i((size_t)VICGPU_SI_NROW(g->opt.Nnode) * n);
+    const int r = vicgpu_get_state(g->ctx[k], d.data(), i.data());
+    if (r == VICGPU_OK) {
+      merge_hru_table(g, k, d, VICGPU_SD_NROW(g->opt.Nnode), sd);
+      merge_hru_table(g, k, i, VICGPU_SI_NROW(g->opt.Nnode), si);
+    }
+    return r;
+  });
+}
+
+int vicgpu_group_set_fluxes(vicgpu_group* g, const double* flux) {
+  if (!g || !flux) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    std::vector<double> f;
+    split_hru_table(g, k, flux, FX_NROW, f);
+    return vicgpu_set_fluxes(g->ctx[k], f.data());
+  });
+}
+
+int vicgpu_group_get_fluxes(vicgpu_group* g, double* flux) {
+  if (!g || !flux) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    std::vector<double> f((size_t)FX_NROW * g->hru[k].size());
+    const int r = vicgpu_get_fluxes(g->ctx[k], f.data());
+    if (r == VICGPU_OK) merge_hru_table(g, k, f, FX_NROW, flux);
+    return r;
+  });
+}
+
+int vicgpu_group_prefetch_forcing(vicgpu_group* g, int nsteps, const double* forcing, const unsigned char* snowflag, const int* dmy) {
+  if (!g || !forcing || !snowflag || !dmy) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    return prefetch_impl(g->ctx[k], nsteps, forcing + g->c0(k), snowflag + g->c0(k), nullptr, dmy, 0.0, 1, g->ncell);
+  });
+}
+
+int vicgpu_group_prefetch_forcing_raw(vicgpu_group* g, int nsteps, const double* raw, const int* dmy, double min_wind_speed, int plapse) {
+  if (!g || !raw || !dmy) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    return prefetch_impl(g->ctx[k], nsteps, nullptr, nullptr, raw + g->c0(k), dmy, min_wind_speed, plapse, g->ncell);
+  });
+}
+
+int vicgpu_group_swap_forcing(vicgpu_group* g) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_swap_forcing(g->ctx[k]); });
+}
+
+int vicgpu_group_push_forcing(vicgpu_group* g, int nsteps, const double* forcing, const unsigned char* snowflag, const int* dmy) {
+  const int r = vicgpu_group_prefetch_forcing(g, nsteps, forcing, snowflag, dmy);
+  return r == VICGPU_OK ? vicgpu_group_swap_forcing(g) : r;
+}
+
+int vicgpu_group_step(vicgpu_group* g, int step0, int nsteps) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_step(g->ctx[k], step0, nsteps); });
+}
+
+int vicgpu_group_synchronize(vicgpu_group* g) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_synchronize(g->ctx[k]); });
+}
+
+int vicgpu_group_put_data_config(vicgpu_group* g, int out_step_ratio) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_put_data_config(g->ctx[k], out_step_ratio); });
+}
+
+int vicgpu_group_put_data_init(vicgpu_group* g) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_put_data_init(g->ctx[k]); });
+}
+
+int vicgpu_group_get_outputs(vicgpu_group* g, int nvar, const int* var_ids, float* out, int reset) {
+  if (!g || nvar < 0 || (nvar > 0 && (!var_ids || !out))) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  for (int v = 0; v < nvar; v++)
+    if (var_ids[v] < 0 || var_ids[v] >= VOUT_NVAR) return group_fail(g, VICGPU_ERR_ARG, "get_outputs: unknown variable id");
+  return group_each(g, [&](int k) { return get_outputs_impl(g->ctx[k], nvar, var_ids, nvar > 0 ? out + g->c0(k) : out, reset, g->ncell); });
+}
+
+int vicgpu_group_get_balance(vicgpu_group* g, double* pb) {
+  if (!g || !pb) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    vicgpu_ctx* c = g->ctx[k];
+    if (!c->put_on) return (int)VICGPU_ERR_STATE;
+    return d2h_cols(c, pb + g->c0(k), g->ncell, c->d_pb, sizeof(double), PB_NROW);
+  });
+}
+
+int vicgpu_group_get_cell_errors(vicgpu_group* g, int* flags) {
+  if (!g || !flags) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->d_cell_err, sizeof(int), 1); });
+}
+
+int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset) {
+  if (!g || !eq) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return glacier_fit_impl(g->ctx[k], eq + g->c0(k), reset, g->ncell); });
+}
+
+// State records: shard k's records are the global records [cell_hru_offset[b[k]], cell_hru_offset[b[k+1]]), in the same order
+int vicgpu_group_get_state_records(vicgpu_group* g, double* rec) {
+  if (!g || !rec) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  const size_t L = VICGPU_SR_LEN(g->opt.Nnode);
+  return group_each(g, [&](int k) { return vicgpu_get_state_records(g->ctx[k], rec + (size_t)g->rec_first[k] * L); });
+}
+
+int vicgpu_group_set_state_records(vicgpu_group* g, const double* rec) {
+  if (!g || !rec) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  // every record of every shard first: a reader that throws changes nothing (vicgpu_set_state_records)
+  const size_t L = VICGPU_SR_LEN(g->opt.Nnode);
+  for (int j = 0; j < g->nhru; j++)
+    if ((int)rec[j * L + SR_BAND_INDEX] != g->rec_band[j] || (int)rec[j * L + SR_VEG_CLASS] != g->rec_veg[j])
+      return group_fail(g, VICGPU_ERR_ARG, "state record " + std::to_string(j) +
+                                               ": band / vegetation class do not match the domain (write_model_state.c:179-188)");
+  return group_each(g, [&](int k) { return vicgpu_set_state_records(g->ctx[k], rec + (size_t)g->rec_first[k] * L); });
+}
+
+}  // extern "C"

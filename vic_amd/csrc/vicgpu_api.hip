@@ -2025,18 +2025,24 @@ static bool is_pinned(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
-// source -> device on the copy stream: straight from pinned memory, through the slot's staging area otherwise
-static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, const void* src, size_t bytes, size_t stage_off) {
-  const void* from = src;
+// source -> device on the copy stream: `rows` rows of `width` bytes, `pitch` bytes apart in the source (pitch > width: a
+// column block of a wider table, vicgpu_group.h) and packed on the device; straight from pinned memory, through the slot's
+// staging area otherwise
+static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, const void* src, size_t width, size_t rows,
+                         size_t pitch, size_t stage_off) {
   if (!is_pinned(src)) {
-    memcpy((char*)sl.h_stage + stage_off, src, bytes);
-    from = (char*)sl.h_stage + stage_off;
+    char* st = (char*)sl.h_stage + stage_off;
+    if (pitch == width) memcpy(st, src, width * rows);
+    else for (size_t r = 0; r < rows; r++) memcpy(st + r * width, (const char*)src + r * pitch, width);
+    return hipMemcpyAsync(dst, st, width * rows, hipMemcpyHostToDevice, c->copy_stream);
   }
-  return hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, c->copy_stream);
+  if (pitch == width) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyHostToDevice, c->copy_stream);
+  return hipMemcpy2DAsync(dst, width, src, pitch, width, rows, hipMemcpyHostToDevice, c->copy_stream);
 }
 
+// ld: cells per row of the source tables (c->ncell, or the global cell count when a group uploads one shard's columns)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
-                         const int* dmy, double min_wind, int plapse) {
+                         const int* dmy, double min_wind, int plapse, int ld) {
   if (!c || nsteps <= 0 || !dmy || (!raw && (!forcing || !snowflag))) return VICGPU_ERR_ARG;
   if (!c->domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2070,7 +2076,7 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
     sl.stage_cap = need_stage;
   }
   if (raw) {
-    HIPCHK(c, upload(c, sl, sl.d_raw, raw, rbytes, 0));
+    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * c->ncell, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
     FArgs a;
     a.nsteps = nsteps; a.ncell = c->ncell; a.dt = c->o.dt; a.snow_step = c->o.snow_step; a.NF = c->o.NF; a.NR = c->o.NR;
     a.temp_th_type = c->o.TEMP_TH_TYPE; a.Nband = c->o.Nband; a.Nnode = c->o.Nnode; a.plapse = plapse;
@@ -2080,8 +2086,8 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
     hipLaunchKernelGGL(vic_derive_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
     HIPCHK(c, hipGetLastError());
   } else {
-    HIPCHK(c, upload(c, sl, sl.d_f, forcing, fbytes, 0));
-    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, sbytes, is_pinned(forcing) ? 0 : fbytes));
+    HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * c->ncell, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->ncell, (size_t)nsteps * nsub, ld, is_pinned(forcing) ? 0 : fbytes));
   }
   HIPCHK(c, hipEventRecord(sl.uploaded, c->copy_stream));
   sl.upload_pending = true;
@@ -2093,11 +2099,11 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
 }
 
 int vicgpu_prefetch_forcing(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const int* dmy) {
-  return prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1);
+  return c ? prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1, c->ncell) : VICGPU_ERR_ARG;
 }
 int vicgpu_prefetch_forcing_raw(vicgpu_ctx* c, int nsteps, const double* raw, const int* dmy, double min_wind_speed, int plapse) {
   if (!raw) return VICGPU_ERR_ARG;
-  return prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse);
+  return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->ncell) : VICGPU_ERR_ARG;
 }
 
 int vicgpu_swap_forcing(vicgpu_ctx* c) {
@@ -2244,6 +2250,18 @@ static int d2h(vicgpu_ctx* c, void* dst, const void* src, size_t bytes) {
   return VICGPU_OK;
 }
 
+// the same for a per-cell table [nrow][ncell] into the columns [0, ncell) of a host table whose rows are ld cells wide (a group
+// reads one shard's columns straight into the caller's global table)
+static int d2h_cols(vicgpu_ctx* c, void* dst, int ld, const void* src, size_t elem, int nrow) {
+  if (!c || !dst || !src || ld < c->ncell) return VICGPU_ERR_ARG;
+  if (ld == c->ncell) return d2h(c, dst, src, elem * nrow * c->ncell);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(dst, elem * ld, src, elem * c->ncell, elem * c->ncell, nrow, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VICGPU_OK;
+}
+
 int vicgpu_get_fluxes(vicgpu_ctx* c, double* flux) { return c ? d2h(c, flux, c->d_flux, sizeof(double) * FX_NROW * c->nhru) : VICGPU_ERR_ARG; }
 int vicgpu_get_cell_outputs(vicgpu_ctx* c, double* o) { return c ? d2h(c, o, c->d_cell_out, sizeof(double) * CO_NROW * c->ncell) : VICGPU_ERR_ARG; }
 int vicgpu_get_accum(vicgpu_ctx* c, double* a) { return c ? d2h(c, a, c->d_accum, sizeof(double) * CA_NROW * c->ncell) : VICGPU_ERR_ARG; }
@@ -2257,8 +2275,8 @@ int vicgpu_reset_accum(vicgpu_ctx* c) {
   return VICGPU_OK;
 }
 
-int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) {
-  if (!c || !c->d_cp || !eq) return VICGPU_ERR_ARG;
+static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld) {
+  if (!c || !c->d_cp || !eq || ld < c->ncell) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   double* d_eq = nullptr;
   HIPCHK(c, hipMalloc(&d_eq, sizeof(double) * GMB_NROW * c->ncell));
@@ -2268,11 +2286,17 @@ int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) {
   hipLaunchKernelGGL(vic_glacier_fit, dim3((c->ncell + 63) / 64), dim3(64), 0, c->stream, g);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = copy_on(c->stream, eq, d_eq, sizeof(double) * GMB_NROW * c->ncell, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && ld == c->ncell) e = copy_on(c->stream, eq, d_eq, sizeof(double) * GMB_NROW * c->ncell, hipMemcpyDeviceToHost);
+  else if (e == hipSuccess) {
+    e = hipMemcpy2DAsync(eq, sizeof(double) * ld, d_eq, sizeof(double) * c->ncell, sizeof(double) * c->ncell, GMB_NROW,
+                         hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
   HIPIGN(hipFree(d_eq));
   HIPCHK(c, e);
   return VICGPU_OK;
 }
+int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) { return c ? glacier_fit_impl(c, eq, reset, c->ncell) : VICGPU_ERR_ARG; }
 
 int vicgpu_debug_pure(vicgpu_ctx* c, int fn, int n, const double* in, double* out) {
   if (!c || !c->d_cp || fn < 0 || fn >= VICGPU_PURE_NFN_DEVICE || n <= 0 || !in || !out) return VICGPU_ERR_ARG;
@@ -2476,8 +2500,9 @@ static int out_rows(const vicgpu_ctx* c, int nvar, const int* ids, std::vector<i
   return (int)rows.size();
 }
 
-int vicgpu_get_outputs(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset) {
-  if (!c || nvar < 0 || (nvar > 0 && (!var_ids || !out))) return VICGPU_ERR_ARG;
+// ld: cells per row of `out` (c->ncell, or the global cell count when a group writes one shard's columns)
+static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld) {
+  if (!c || nvar < 0 || (nvar > 0 && (!var_ids || !out)) || ld < c->ncell) return VICGPU_ERR_ARG;
   if (!c->put_on) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<int> rows;
@@ -2494,12 +2519,20 @@ int vicgpu_get_outputs(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, 
       hipLaunchKernelGGL(vic_out_rows_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out_agg, d_rows, nr, c->ncell, d_f);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = copy_on(c->stream, out, d_f, sizeof(float) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && ld == c->ncell) e = copy_on(c->stream, out, d_f, sizeof(float) * n, hipMemcpyDeviceToHost);
+    else if (e == hipSuccess) {
+      e = hipMemcpy2DAsync(out, sizeof(float) * ld, d_f, sizeof(float) * c->ncell, sizeof(float) * c->ncell, nr, hipMemcpyDeviceToHost,
+                           c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
     HIPIGN(hipFree(d_rows)); HIPIGN(hipFree(d_f));
     HIPCHK(c, e);
   }
   if (reset) HIPCHK(c, fill_on(c->stream, c->d_out_agg, 0, sizeof(double) * (size_t)c->out_nrow * c->ncell));   // vicNl.c:599-606
   return VICGPU_OK;
+}
+int vicgpu_get_outputs(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset) {
+  return c ? get_outputs_impl(c, nvar, var_ids, out, reset, c->ncell) : VICGPU_ERR_ARG;
 }
 
 int vicgpu_get_output_data(vicgpu_ctx* c, int nvar, const int* var_ids, int which, double* out) {
@@ -2533,3 +2566,6 @@ int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
 }
 
 }  // extern "C"
+
+// the device group (include/vicgpu_group.h): host code on top of the entries above
+#include "vic_group.hpp"
