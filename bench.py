@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the VIC hot path (dist_prec -> full_energy -> surface_fluxes) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg4|cfg2] [--compat] [--node-solver newton|brent]
-                    [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg4|cfg2|cfg5] [--compat] [--node-solver newton|brent]
+                    [--dump-outputs DIR] [--full]
 
 K is the number of timed steps (cfg5: a multiple of 24, whole output records); `ms_per_step` in the JSON line is the wall
 time of the timed region over K.  `--dump-outputs DIR` writes what the timed path computed (bench.dump_outputs) as .npy
 files; the inputs depend on the arguments only, so two builds can be compared output for output.
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes its outputs when
+`--dump-outputs` is given and prints the JSON line.  `--full` adds the measurements that take runs of their own, after the
+timed region: at N = 1 the other node solver, `--compat` and streamed forcing legs and the CPU baseline, and for cfg5 the
+resident-forcing leg, the upload of one chunk on its own and the state save.  Without `--full` their figures are null.
 
 A "step" is one model time step of every cell of the rank's shard (all HRUs, all snow sub-steps) INCLUDING its put_data
 (dist_prec.c:167): the aggregated output variables are updated on the device every step, and the table the writer needs
@@ -16,8 +21,8 @@ Metric: cell-timesteps/s, whole job (sum over ranks).
 
 Node solver.  The frozen-node root finds of the soil profile run as a safeguarded Newton iteration by default (outputs
 within north_star's 1e-5 of the reference: tests/test_gpu_parity.py::test_gpu_against_reference_goldens[*-newton]);
-`--node-solver brent` replays the reference's Brent iteration step by step (1e-6 on every state variable).  At N = 1 the
-JSON line also carries the step time of the other mode (`strict_replay_ms_per_step`), measured after the timed region.
+`--node-solver brent` replays the reference's Brent iteration step by step (1e-6 on every state variable).  With `--full` at
+N = 1 the JSON line also carries the step time of the other mode (`strict_replay_ms_per_step`), measured after the timed region.
 
 Launching.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts N ranks itself (one process per GPU,
 `python -m torch.distributed.run --nproc-per-node N ...`, RCCL) BEFORE anything in this process touches the GPU, waits
@@ -314,8 +319,9 @@ def cfg5_sequence(m, f, dmy, step0, nsteps, chunk, out_every, opt, gather, bufs=
 
 
 def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_dist, ncell, ncell_global):
-    """`--config cfg5`: K steps of cfg5_sequence in the timed region, the same K steps with the forcing resident beside it, the
-    upload + derivation of one chunk on its own (how much of it the overlap hides), and the state records at the end."""
+    """`--config cfg5`: K steps of cfg5_sequence in the timed region; with `--full` also the same K steps with the forcing
+    resident beside it, the upload + derivation of one chunk on its own (how much of it the overlap hides), and the state
+    records at the end."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -343,24 +349,26 @@ def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_di
         m = Model(d, device=local_rank)
         m.set_state(sd0, si0); m.set_write_fluxes(False); m.put_data_config(OUT_STEP_RATIO); m.put_data_init()
         return m
-    # resident leg: the same steps with the whole forcing table already in HBM
-    m0 = make()
-    raw_all = np.zeros((W + K, C_()["VIC_NRAW"], opt.dt, ncell))
-    for name, src, scale in RAW_FROM_TABLE:
-        raw_all[:, C_()[name]] = f[:W + K, C_()[src], :opt.NF] * scale
-    m0.prefetch_forcing_raw(raw_all, dmy[:W + K]); m0.swap_forcing(); m0.synchronize()       # the same records, derived at once
-    del raw_all
-    if W:
-        m0.dist_prec(0, W, sync=True)
-        m0.get_outputs(OUT_VARS, reset=True)
-    barrier(); t0 = time.perf_counter()
-    for k in range(K // OUT_STEP_RATIO):
-        m0.dist_prec(W + k * OUT_STEP_RATIO, OUT_STEP_RATIO, sync=False)
-        m0.get_outputs(OUT_VARS, reset=True)
-    m0.synchronize(); barrier()
-    resident_ms = (time.perf_counter() - t0) / K * 1e3
-    state_ref = m0.get_state()
-    m0.close()
+    resident_ms = state_ref = None
+    if args.full:
+        # resident leg: the same steps with the whole forcing table already in HBM
+        m0 = make()
+        raw_all = np.zeros((W + K, C_()["VIC_NRAW"], opt.dt, ncell))
+        for name, src, scale in RAW_FROM_TABLE:
+            raw_all[:, C_()[name]] = f[:W + K, C_()[src], :opt.NF] * scale
+        m0.prefetch_forcing_raw(raw_all, dmy[:W + K]); m0.swap_forcing(); m0.synchronize()       # the same records, derived at once
+        del raw_all
+        if W:
+            m0.dist_prec(0, W, sync=True)
+            m0.get_outputs(OUT_VARS, reset=True)
+        barrier(); t0 = time.perf_counter()
+        for k in range(K // OUT_STEP_RATIO):
+            m0.dist_prec(W + k * OUT_STEP_RATIO, OUT_STEP_RATIO, sync=False)
+            m0.get_outputs(OUT_VARS, reset=True)
+        m0.synchronize(); barrier()
+        resident_ms = (time.perf_counter() - t0) / K * 1e3
+        state_ref = m0.get_state()
+        m0.close()
     # streamed leg (the timed one)
     m = make()
     bufs = [m.pinned((CH, C_()["VIC_NRAW"], opt.dt, ncell)) for _ in range(2)]
@@ -376,25 +384,28 @@ def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_di
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    kernel_ms, nlaunch = m.last_kernel_ms()
-    same = all(np.array_equal(a, b, equal_nan=True) for a, b in zip(m.get_state(), state_ref))
+    same = None
+    if state_ref is not None:
+        same = all(np.array_equal(a, b, equal_nan=True) for a, b in zip(m.get_state(), state_ref))
     nerr = int((m.get_cell_errors() != 0).sum())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, m, tables[-1])
-    # one chunk's upload + derivation on its own
-    fs = f[W:W + CH]
-    for name, src, scale in RAW_FROM_TABLE:
-        bufs[0][:, C_()[name]] = fs[:, C_()[src], :opt.NF] * scale
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    m.prefetch_forcing_raw(bufs[0], dmy[W:W + CH]); m.swap_forcing(); m.synchronize()
-    upload_ms = (time.perf_counter() - t0) / CH * 1e3
-    # state save: the records in state-file order (write_model_state.c:95-337) to the host
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    rec = m.get_state_records()
-    state_save_ms = (time.perf_counter() - t0) * 1e3
+    upload_ms = state_save_ms = rec = None
+    if args.full:
+        # one chunk's upload + derivation on its own
+        fs = f[W:W + CH]
+        for name, src, scale in RAW_FROM_TABLE:
+            bufs[0][:, C_()[name]] = fs[:, C_()[src], :opt.NF] * scale
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        m.prefetch_forcing_raw(bufs[0], dmy[W:W + CH]); m.swap_forcing(); m.synchronize()
+        upload_ms = (time.perf_counter() - t0) / CH * 1e3
+        # state save: the records in state-file order (write_model_state.c:95-337) to the host
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        rec = m.get_state_records()
+        state_save_ms = (time.perf_counter() - t0) * 1e3
     m.close()
     streamed_ms = elapsed / K * 1e3
-    hidden = 1.0 - max(0.0, streamed_ms - resident_ms) / upload_ms if upload_ms > 0 else None
+    hidden = 1.0 - max(0.0, streamed_ms - resident_ms) / upload_ms if upload_ms else None
     if rank != 0:
         return None
     hru_per_cell = d.nhru // d.ncell
@@ -408,7 +419,8 @@ def run_cfg5(args, cfg, d, f, sf, dmy, sd0, si0, world, rank, local_rank, use_di
                    "resident_forcing_ms_per_step": resident_ms, "chunk_upload_and_derive_ms_per_step": upload_ms, "h2d_hidden_frac": hidden,
                    "output_records_gathered": len(tables), "output_gather_ms": float(np.mean(gather_ms)) if gather_ms else None,
                    "output_table": "%s as float32 [%d][%d]" % (",".join(OUT_VARS), tables[0].shape[0], tables[0].shape[1]) if tables and tables[0] is not None else None,
-                   "state_save_ms": state_save_ms, "state_record_bytes": int(rec.nbytes), "streamed_state_equals_resident": bool(same),
+                   "state_save_ms": state_save_ms, "state_record_bytes": int(rec.nbytes) if rec is not None else None,
+                   "streamed_state_equals_resident": same, "full": args.full,
                    "cells_with_error_flags": nerr,
                    "parallelism": "cells sharded across %d GPU(s), output table gathered to rank 0 every %d steps" % (world, OUT_STEP_RATIO)},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
@@ -432,11 +444,16 @@ def main():
     ap.add_argument("--compat", action="store_true", help="FROZEN_SOIL as the reference ships it (frozen_soil.c:218-221) instead of 'fixed'")
     ap.add_argument("--node-solver", default="newton", choices=["newton", "brent"],
                     help="frozen-node root finder (vicgpu_options.NODE_SOLVER): converged Newton (default) or the reference's Brent iteration replayed")
-    ap.add_argument("--no-strict-leg", action="store_true", help="skip the second timing with the other node solver (N = 1)")
-    ap.add_argument("--no-stream-leg", action="store_true", help="skip the PCIe-inclusive timing (forcing streamed in chunks, N = 1)")
-    ap.add_argument("--no-compat-leg", action="store_true", help="skip the 4-step timing of frozen_compat = 1 (the reference's FROZEN_SOIL as shipped, N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the measurements that take runs of their own: at N = 1 the other node solver, "
+                         "--compat and streamed-forcing legs and the CPU baseline; for cfg5 the resident-forcing leg, one chunk's "
+                         "upload and the state save")
+    ap.add_argument("--no-strict-leg", action="store_true", help="with --full: skip the second timing with the other node solver (N = 1)")
+    ap.add_argument("--no-stream-leg", action="store_true", help="with --full: skip the PCIe-inclusive timing (forcing streamed in chunks, N = 1)")
+    ap.add_argument("--no-compat-leg", action="store_true",
+                    help="with --full: skip the 4-step timing of frozen_compat = 1 (the reference's FROZEN_SOIL as shipped, N = 1)")
     ap.add_argument("--ncell", type=int, default=0, help="override cells per GPU (debug only; invalidates the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed (the writer's output table, the last step's "
@@ -537,7 +554,6 @@ def main():
         elapsed = float(t.item())
     kernel_ms, nlaunch = m.last_kernel_ms()
     nerr = int((m.get_cell_errors() != 0).sum())
-    acc = m.get_accum()
     # the writer's table: the aggregates of OUT_VARS as float32 [rows][cells] (WriteOutputNetCDF.c:387-455), fetched once per
     # output record -- outside the timed region (it happens every OUT_STEP_RATIO steps, not per model step)
     barrier()
@@ -557,14 +573,15 @@ def main():
         nerr = int(nerr_t.item())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, m, full)
+    m.close()
+    extras = args.full and world == 1      # the legs below: --full at N = 1 only
     # the same K steps with the other node solver (N = 1): what the choice of solver costs / buys
     other_ms = None
-    if world == 1 and not opt.QUICK_FLUX and not args.no_strict_leg:
+    if extras and not opt.QUICK_FLUX and not args.no_strict_leg:
         import copy
         d2 = copy.copy(d)
         d2.opt = copy.copy(opt)
         d2.opt.NODE_SOLVER = C["VIC_NODE_SOLVER_BRENT"] if args.node_solver == "newton" else C["VIC_NODE_SOLVER_NEWTON"]
-        m.close()
         m2 = make_model(d2)
         if W > 0:
             m2.dist_prec(0, W, sync=True)
@@ -577,7 +594,7 @@ def main():
     # FROZEN_SOIL exactly as the reference ships it (frozen_soil.c:218-221, SURVEY.md Finding 1.2 / 8(d) "both reported"): a few
     # steps of the same workload with frozen_compat = 1
     compat_ms = None
-    if world == 1 and opt.FROZEN_SOIL and not opt.frozen_compat and not args.no_compat_leg:
+    if extras and opt.FROZEN_SOIL and not opt.frozen_compat and not args.no_compat_leg:
         import copy
         d4 = copy.copy(d)
         d4.opt = copy.copy(opt)
@@ -593,7 +610,7 @@ def main():
     # PCIe-inclusive rate (N = 1): the same K steps with the forcing arriving as hourly RAW values in chunks of 6 steps from
     # pinned host memory, each chunk uploading (and derived on the device) while the previous one runs
     stream_ms = None
-    if world == 1 and not args.no_stream_leg and opt.snow_step == 1:
+    if extras and not args.no_stream_leg and opt.snow_step == 1:
         m3 = Model(d, device=local_rank)
         m3.set_state(sd0, si0); m3.set_write_fluxes(False); m3.put_data_config(OUT_STEP_RATIO); m3.put_data_init()
         CH = 6
@@ -638,7 +655,7 @@ def main():
                        "frozen_soil_semantics": ("compat" if opt.frozen_compat else "fixed") if opt.FROZEN_SOIL else None,
                        "parallelism": "cells sharded across %d GPU(s) (one process per GPU, contiguous blocks of one domain), no data-path collective" % world,
                        "ranks_seen_by_rccl": ranks_seen if use_dist else None,
-                       "node_solver": args.node_solver,
+                       "node_solver": args.node_solver, "full": args.full,
                        ("strict_replay_ms_per_step" if args.node_solver == "newton" else "newton_ms_per_step"): other_ms,
                        "streamed_raw_forcing_ms_per_step": stream_ms,
                        "compat_ms_per_step": compat_ms,
@@ -659,13 +676,14 @@ def main():
                                  "profiles/ holds the per-kernel rocprofv3 stats and PMC passes"},
         }
         out["roofline_valu"] = valu_roofline(cfg_name, value / world)       # per GPU
-        if not args.no_cpu_baseline and world == 1:
+        if extras and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg)
             except Exception as e:  # the baseline is a reported extra; never lose the bench line over it
                 out["cpu_baseline"] = {"value": None, "unit": "cell-timesteps/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
         elif world == 1:
-            out["cpu_baseline"] = {"value": None, "unit": "cell-timesteps/s", "cores": 0, "kind": "port", "sample": "skipped (--no-cpu-baseline)"}
+            out["cpu_baseline"] = {"value": None, "unit": "cell-timesteps/s", "cores": 0, "kind": "port",
+                                   "sample": "skipped (--no-cpu-baseline)" if args.full else "not measured (a plain run; --full times it)"}
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

@@ -1,8 +1,9 @@
 """bench.py's own launcher (CPU test): `python bench.py --gpus N` with no WORLD_SIZE in the environment must start N
 ranks itself -- one process per GPU through torch.distributed.run -- before it touches the GPU; a rank count that does
 not match --gpus is an error, never a silent 1-GPU run.  `--launch-check` makes the ranks rendezvous over gloo and
-report instead of benchmarking, so the test needs no GPU.  Also: --steps is honoured exactly, and --dump-outputs writes
-finite, bounded, repeatable files (on a stand-in model here, on a real one in the GPU test)."""
+report instead of benchmarking, so the test needs no GPU.  Also: --steps is honoured exactly, --dump-outputs writes
+finite, bounded, repeatable files (on a stand-in model here, on a real one in the GPU test), and a plain run leaves the
+measurements that take runs of their own to --full (GPU test)."""
 import json
 import os
 import subprocess
@@ -129,3 +130,34 @@ def test_dump_outputs_of_a_model_are_finite(cfg_name, tmp_path):
         assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
     assert np.array_equal(np.load(tmp_path / "state_double_defined.npy") == 1, ~np.isnan(sd))
     assert np.array_equal(np.load(tmp_path / "output_table.npy"), table)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg_name,steps,warmup", [("cfg3", 6, 1), ("cfg5", 24, 6)])
+def test_plain_run_leaves_the_extra_legs_to_full(cfg_name, steps, warmup):
+    """A plain run prints the headline line with the extra legs' figures null; --full measures them after the timed region
+    (the CPU baseline, host time only, is left out here).  Small domains via --ncell."""
+    def run(*extra):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", cfg_name, "--ncell", "2000",
+                            "--steps", str(steps), "--warmup", str(warmup)] + list(extra), env=_env(), cwd=ROOT,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+    plain = run()
+    full = run("--full", "--no-cpu-baseline")
+    for r in (plain, full):
+        assert r["metric"] == "cell-timesteps/s" and r["unit"] == "cell-timesteps/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "f64" and r["steps"] == steps and r["value"] > 0 and r["ms_per_step"] > 0
+        assert r["config"]["cells_with_error_flags"] == 0
+    assert plain["config"]["full"] is False and full["config"]["full"] is True
+    if cfg_name == "cfg3":
+        legs = ("strict_replay_ms_per_step", "compat_ms_per_step", "streamed_raw_forcing_ms_per_step")
+        assert plain["cpu_baseline"]["value"] is None and plain["cpu_baseline"]["sample"].startswith("not measured")
+    else:
+        legs = ("resident_forcing_ms_per_step", "chunk_upload_and_derive_ms_per_step", "state_save_ms")
+        assert plain["config"]["streamed_state_equals_resident"] is None
+        assert full["config"]["streamed_state_equals_resident"] is True and full["config"]["state_record_bytes"] > 0
+    for k in legs:
+        assert plain["config"][k] is None and full["config"][k] > 0, k
