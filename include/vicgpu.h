@@ -25,7 +25,8 @@
  * QUICK_FS / LOW_RES_MOIST / CLOSE_ENERGY (all compiled out in the reference,
  * user_def.h:36-92).  CORRPREC, BLOWING, IMPLICIT (finite-difference soil profile, node-array
  * freezing parameters: frozen_compat = 0) and QUICK_SOLVE (with NOFLUX / EXP_TRANS as the reference handles them)
- * are implemented.  What the device code does not implement (see vicgpu_create) is
+ * are implemented.  Nnode runs up to the reference's MAX_NODES = 50 (kernels instantiated for 10, up to 24 and up
+ * to 50 nodes); IMPLICIT up to 24.  What the device code does not implement (see vicgpu_create) is
  * REJECTED with VICGPU_ERR_UNSUPPORTED, never silently replaced.
  */
 #ifndef VICGPU_H_
@@ -40,7 +41,7 @@ extern "C" {
 #define VICGPU_ABI_VERSION 3
 
 #define VIC_NLAYER        3    /* MAX_LAYERS, user_def.h:95 */
-#define VIC_MAX_NODES    24    /* device build limit for options.Nnode (reference MAX_NODES = 50, user_def.h:96) */
+#define VIC_MAX_NODES    50    /* MAX_NODES, user_def.h:96: the largest options.Nnode (IMPLICIT: 24, see vicgpu_options) */
 #define VIC_MAX_BANDS    30    /* MAX_BANDS, user_def.h:97 */
 #define VIC_N_PET_TYPES   6    /* vicNl_def.h:213 */
 #define VIC_MAX_ZWTVMOIST 11   /* user_def.h:100 */
@@ -76,7 +77,7 @@ extern "C" {
 typedef struct vicgpu_options {
   int abi_version;          /* must be VICGPU_ABI_VERSION */
   int Nlayer;               /* must be 3 */
-  int Nnode;                /* 3 with QUICK_FLUX; <= VIC_MAX_NODES */
+  int Nnode;                /* 3 with QUICK_FLUX; 3 .. VIC_MAX_NODES (get_global_param.c:1193) */
   int Nband;                /* options.SNOW_BAND */
   int dt;                   /* global_param.dt, hours */
   int snow_step;            /* options.SNOW_STEP, hours (== dt when dt < 24, get_global_param.c:965) */
@@ -98,7 +99,8 @@ typedef struct vicgpu_options {
   int nveg_types;           /* veg_lib[0].NVegLibTypes; the table holds nveg_types + 4 rows */
   int CORRPREC;             /* gauge-undercatch correction of precipitation (correct_precip.c, full_energy.c:188-194) */
   int IMPLICIT;             /* options.IMPLICIT: Newton-Raphson soil heat solver (frozen_soil.c:229-301, newt_raph_func_fast.c),
-                               the explicit solver as its fallback; rejected with QUICK_FLUX or frozen_compat */
+                               the explicit solver as its fallback; rejected with QUICK_FLUX, frozen_compat or Nnode > 24
+                               (the reference's own limit is 21 nodes: MAXSIZE 20, newt_raph_func_fast.c:7) */
   int BLOWING;              /* options.BLOWING: sublimation from blowing snow (CalcBlowingSnow.c), once per snow sub-step */
   int QUICK_SOLVE;          /* options.QUICK_SOLVE (calc_surf_energy_bal.c:289-314, 400-475): ignored with QUICK_FLUX (as in the
                                reference); the iteration runs with NOFLUX and EXP_TRANS forced off, NOFLUX comes back with a second

@@ -44,6 +44,12 @@ RESOURCE_LIMITS = {
     "vic_hru_step<10, true>": (256, 2200),
     "vic_fd_stage<10, true, false>": (256, 800),
     "vic_fd_stage<10, false, false>": (256, 600),
+    # the deep node bound (25 .. 50 nodes): scratch-heavy instantiations of the same kind, policed the same way
+    "vic_hru_step<50, true>": (256, 5200),
+    "vic_fd_stage<50, true, false>": (256, 4500),
+    "vic_fd_stage<50, true, true>": (256, 4500),
+    "vic_fd_stage<50, false, false>": (256, 5300),
+    "vic_fd_stage<50, false, true>": (256, 6300),
     "vic_surf_eval": (256, 0),
     "vic::vic_profile_solve_reg<10": (256, 128),
     "vic::vic_profile_solve_lockstep": (256, 0),

@@ -35,7 +35,7 @@ struct IArgs {
 };
 
 struct ImplicitSolver {
-  static constexpr int M = VIC_MAX_NODES + 2;
+  static constexpr int M = VIC_MID_NODES + 2;       // IMPLICIT runs up to 24 nodes (vicgpu_create); its records use ok bit 32
   int n, NOFLUX, EXP_TRANS;
   double deltat, Bexp, Ts, Tb;
   double T0[M], moist[M], ice[M], kappa[M], Cs[M];

@@ -36,8 +36,9 @@ namespace vic {
 
 // Work lists are kept in NBUCKET segments by a per-HRU key (the number of frozen nodes at the start of the step, and
 // whether a node sits within SOIL_DT of 0 C -- see vic_fd_stage): the profile kernel takes the segments one after the
-// other, most expensive first, so that the HRUs a wave works on at any time have the same nodes frozen.
-constexpr int NBUCKET = 2 * (VIC_MAX_NODES + 2);
+// other, most expensive first, so that the HRUs a wave works on at any time have the same nodes frozen.  The deep bound
+// (more than VIC_MID_NODES nodes) shares these segments: its frozen-node counts of 25 and more take the top one of each half.
+constexpr int NBUCKET = 2 * (VIC_MID_NODES + 2);
 static_assert(NBUCKET <= 64, "one lane per work-list segment when the pending total is summed");
 
 struct PArgs {
@@ -60,10 +61,11 @@ struct PArgs {
   const int* jl;                     // QUICK_SOLVE: [nhru] nodes 1 .. jl - 1 are solved (calc_surf_energy_bal.c:289-299), or null: all
 };
 
-// One solution record: T[Nn], {fbmask | ok << 32}, int fallback counts [Nn].  Every HRU keeps the records of its last
-// two solves together with the trial temperatures they belong to: the Brent iteration on Tsurf ends with one more
-// evaluation AT the root, which is one of the last two trial points unless the solver fell back -- the same inputs give
-// the same profile bit for bit, so that solve is looked up instead of repeated (vic_surf_eval).
+// One solution record: T[Nn], {fbmask | ok << NodeBound<NN>::ok_bit} (ok in bit 32 up to 24 nodes, in bit 63 above),
+// int fallback counts [Nn].  Every HRU keeps the records of its last two solves together with the trial temperatures
+// they belong to: the Brent iteration on Tsurf ends with one more evaluation AT the root, which is one of the last two
+// trial points unless the solver fell back -- the same inputs give the same profile bit for bit, so that solve is looked
+// up instead of repeated (vic_surf_eval).
 __host__ __device__ inline int pout_stride(int Nn) { return Nn + 1 + (Nn + 1) / 2; }
 __host__ __device__ inline int pout_hru_stride(int Nn) { return 2 * pout_stride(Nn) + 2; }
 __host__ __device__ inline int pout_key(int Nn, int slot) { return 2 * pout_stride(Nn) + slot; }
@@ -247,10 +249,26 @@ VIC_DEV double node_visit(bool sweeping, bool frozen_on, bool EXP_TRANS, const N
   return x;
 }
 
+// the flags of nodes 0 .. n-1 (n <= NN)
+template <int NN>
+VIC_DEV typename NodeBound<NN>::mask_t node_mask_below(int n) {
+  using mask_t = typename NodeBound<NN>::mask_t;
+  constexpr int W = 8 * (int)sizeof(mask_t);
+  return (n >= W) ? ~mask_t(0) : ((mask_t(1) << n) - mask_t(1));
+}
+
+// flags + ok as the record's word
+template <int NN>
+VIC_DEV double profile_flag_word(typename NodeBound<NN>::mask_t fbmask, bool ok) {
+  return __longlong_as_double((long long)((unsigned long long)fbmask | ((unsigned long long)(ok ? 1 : 0) << NodeBound<NN>::ok_bit)));
+}
+
 // the end of a solve: cold-nose hack, non-convergence, fallback bookkeeping (frozen_soil.c:470-493); T / T0 accessors differ
 // between the two kernels, so this is a macro-free helper over plain arrays of the lane's column
+// (the register-resident kernel only: 10 nodes, a 32-bit mask)
 template <int NN>
 VIC_DEV void profile_finish(int Nn, bool TFALLBACK, bool converged, bool& ok, unsigned& fbmask, double* T, const double* T0, int* cnt_add) {
+  static_assert(NN <= 32, "32-bit fall-back mask");
 #pragma unroll
   for (int k = 0; k < NN; k++) cnt_add[k] = 0;
   if (ok && TFALLBACK) {      // cold-nose hack, frozen_soil.c:470-484 (sic: Tlast[j+1] - T[j]); Tlast == T0
@@ -447,17 +465,22 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
 }
 
 // ------------------------------------------------------------------------------------------------
-// any node count: node columns in LDS, the node's record read at each visit
+// any node count: node columns in LDS, the node's record read at each visit.  The start column T0 is in LDS up to
+// VIC_MID_NODES nodes; the deep bound (up to 50 nodes, where both columns would take 51 KB of LDS per wave) takes T0 of
+// node j >= 1 from the node's record, which the visit reads anyway, and T0 of node 0 (the trial surface temperature)
+// from a register: 25.6 KB per wave
 // ------------------------------------------------------------------------------------------------
 constexpr int LS_WAVES = 2;
 template <int NN, bool NEWTON>
 __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_profile_solve_lockstep(const PArgs a) {
+  using mask_t = typename NodeBound<NN>::mask_t;
+  constexpr bool T0_LDS = NN <= VIC_MID_NODES;
   __shared__ int bcount[NBUCKET];
   __shared__ double Tl[NN * 64];
-  __shared__ double T0l[NN * 64];
+  __shared__ double T0l[T0_LDS ? NN * 64 : 1];
   const int lane = threadIdx.x;
 #define T(j) Tl[(j) * 64 + lane]
-#define T0(j) T0l[(j) * 64 + lane]
+#define T0(j) (T0_LDS ? T0l[(T0_LDS ? (j) : 0) * 64 + lane] : ((j) == 0 ? T0s : blk[(j) * PREC + PR_T0]))
   for (int b = lane; b < NBUCKET; b += 64) bcount[b] = a.count[b];
   if (blockIdx.x == 0) {
     for (int b = lane; b < NBUCKET; b += 64) a.count_zero[b] = 0;
@@ -473,7 +496,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
   for (int b = 0; b < NBUCKET; b++) n += bcount[b];
   if ((int)blockIdx.x * 64 >= n) return;
 
-  const int Nn = (NN == VIC_MAX_NODES) ? a.Nn : NN;
+  const int Nn = node_count<NN>(a.Nn);
   const int jlast = a.NOFLUX ? Nn : Nn - 1;
   const int MAXIT = 1000;
   const double threshold = 1.e-2;
@@ -483,8 +506,9 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
 #define LS_CNT(j) (reinterpret_cast<int*>(LS_REC() + Nn + 1)[j])
   bool have = false, sweeping = false, converged = false, ok = true, frozen_on = false;
   int hru = 0, ps = 0, it = 1, jl_lane = 0;
-  unsigned fbmask = 0;
+  mask_t fbmask = 0;
   const double* __restrict__ blk = a.pin;
+  double T0s = 0;                                  // T0 of node 0 when T0 is not in LDS
   bool more = true;
   while (true) {
     const unsigned long long idle = __ballot(!have);
@@ -504,7 +528,12 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
         const double Ts = a.ts[hru];
 #pragma unroll
         for (int k = 0; k < NN; k++)
-          if (k < Nn) { const double t = (k == 0) ? Ts : blk[k * PREC + PR_T0]; T0(k) = t; T(k) = t; LS_CNT(k) = 0; }
+          if (k < Nn) {
+            const double t = (k == 0) ? Ts : blk[k * PREC + PR_T0];
+            if constexpr (T0_LDS) T0l[k * 64 + lane] = t;
+            T(k) = t; LS_CNT(k) = 0;
+          }
+        T0s = Ts;
         have = true; fbmask = 0; ok = true; it = 1;
         converged = (jlast <= 1);
         sweeping = !converged;
@@ -533,7 +562,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
           else newT = node_visit<false, NEWTON>(swj, frozen_on, EXP_TRANS, K, oldT, Tdn, Tup, T0j, failed);
           if (swj) {
             if (failed) {
-              if (a.TFALLBACK) { newT = T0j; fbmask |= (1u << j); LS_CNT(j) += 1; }
+              if (a.TFALLBACK) { newT = T0j; fbmask |= (mask_t(1) << j); LS_CNT(j) += 1; }
               else { ok = false; sweeping = false; }
             }
             if (sweeping) {
@@ -558,7 +587,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
           const double Tk = T(k), Tm = T(k - 1), Tp = T(k + 1), Lk = T0(k), Lm = T0(k - 1), Lp = T0(k + 1);
           if (Lm - Lk > 0 && Lp - Tk > 0 && (Tm - Tk) - (Lm - Lk) > 0 && (Tp - Tk) - (Lp - Lk) > 0) {
             T(k) = 0.5 * (Tm + Tp);
-            fbmask |= (1u << k);
+            fbmask |= (mask_t(1) << k);
             LS_CNT(k) += 1;
           }
         }
@@ -567,13 +596,13 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
         if (a.TFALLBACK) {
 #pragma unroll 1
           for (int k = 0; k < nq; k++) { T(k) = T0(k); LS_CNT(k) += 1; }
-          fbmask |= (nq >= 32) ? 0xFFFFFFFFu : ((1u << nq) - 1u);
+          fbmask |= node_mask_below<NN>(nq);
         } else ok = false;
       }
       double* __restrict__ rec = LS_REC();
 #pragma unroll 1
       for (int k = 0; k < Nn; k++) rec[k] = T(k);
-      rec[Nn] = __longlong_as_double((long long)((unsigned long long)fbmask | ((unsigned long long)(ok ? 1 : 0) << 32)));
+      rec[Nn] = profile_flag_word<NN>(fbmask, ok);
       a.pout[(size_t)hru * pout_hru_stride(Nn) + pout_key(Nn, ps)] = T0(0);
       have = false;
     }

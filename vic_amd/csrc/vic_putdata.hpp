@@ -44,6 +44,8 @@ struct OutLayout {
   int agg[VOUT_NVAR];
 };
 constexpr int VOUT_MAX_ROWS = 1280;   // > 110 + 7*3 + 2*MAX_NODES + 34*MAX_BANDS + 2*MAX_FRONTS
+static_assert(110 + 7 * VIC_NLAYER + 2 * VIC_MAX_NODES + 34 * VIC_MAX_BANDS + 2 * VIC_MAX_FRONTS <= VOUT_MAX_ROWS,
+              "the output table layout covers VIC_MAX_NODES nodes x 2 node variables");
 
 struct OArgs {
   Opt o;
@@ -97,7 +99,9 @@ VIC_DEV PutHru put_hru(const OArgs& a, const CellView& cv, int g) {
 // PART 0: collect_wb_terms (put_data.c:762-948, mu = 1, lakefactor = 1, TreeAdjustFactor = 1) and the partial areas
 // PART 1: collect_eb_terms, the cell-wide part (put_data.c:950-1135)
 // PART 2: collect_eb_terms, the band variables (put_data.c:1137-1232) and OUT_ELEV_BAND
-template <int PART>
+// DEEP (Nnode > VIC_MID_NODES): the node rows of PART 1 are summed node by node straight into the table instead of in
+// per-node registers, which keeps the per-node arrays of vic_put_sum at VIC_MID_NODES
+template <int PART, bool DEEP>
 VIC_DEV void put_sum_part(const OArgs& a, int c) {
   const size_t nh = a.nhru, nc = a.ncell;
   const Opt& o = a.o;
@@ -210,9 +214,10 @@ VIC_DEV void put_sum_part(const OArgs& a, int c) {
     ROW(GLAC_OUTFLOW, 0) = GLAC_OUTFLOW; ROW(GLAC_OUTFLOW_COEF, 0) = GLAC_OUTFLOW_COEF;
   }
   if (PART == 1) {
-    double FDEPTH[3] = {0, 0, 0}, TDEPTH[3] = {0, 0, 0}, TNODE[VIC_MAX_NODES], FBNODE[VIC_MAX_NODES];
+    constexpr int NA = DEEP ? 1 : VIC_MID_NODES;        // per-node sums held in registers
+    double FDEPTH[3] = {0, 0, 0}, TDEPTH[3] = {0, 0, 0}, TNODE[NA], FBNODE[NA];
 #pragma unroll
-    for (int n = 0; n < VIC_MAX_NODES; n++) { TNODE[n] = 0; FBNODE[n] = 0; }
+    for (int n = 0; n < NA; n++) { TNODE[n] = 0; FBNODE[n] = 0; }
     double SURF_FROST_FRAC = 0, BARESOILT = 0, VEGT = 0, SURF_TEMP = 0, SURFT_FBFLAG = 0, SNOWT_FBFLAG = 0, TFOL_FBFLAG = 0, TCAN_FBFLAG = 0,
            GLAC_TSURF_FBFLAG = 0, NET_SHORT = 0, NET_LONG = 0, IN_LONG = 0, ALBEDO = 0, LATENT = 0, LATENT_SUB = 0, SENSIBLE = 0, GRND_FLUX = 0,
            DELTAH = 0, FUSION = 0, ENERGY_ERROR = 0, RAD_TEMP = 0, DELTACC = 0, ADVECTION = 0, SNOW_FLUX = 0, RFRZ_ENERGY = 0, MELT_ENERGY = 0,
@@ -244,12 +249,14 @@ VIC_DEV void put_sum_part(const OArgs& a, int c) {
         else VEGT += (rad_temp - KELVIN) * AreaFactor;
       }
       SURF_TEMP += Tsurf * AreaFactor;
+      if constexpr (!DEEP) {
 #pragma unroll
-      for (int n = 0; n < VIC_MAX_NODES; n++) {
-        if (n < Nn) {
-          TNODE[n] += SD(VICGPU_SD_NODE(SDN_T, n, Nn)) * AreaFactor;
-          FBNODE[n] += SI(VICGPU_SI_NODE(SIN_T_FBFLAG, n, Nn)) * AreaFactor;
-          fb_tsoil += SI(VICGPU_SI_NODE(SIN_T_FBCOUNT, n, Nn));
+        for (int n = 0; n < NA; n++) {
+          if (n < Nn) {
+            TNODE[n] += SD(VICGPU_SD_NODE(SDN_T, n, Nn)) * AreaFactor;
+            FBNODE[n] += SI(VICGPU_SI_NODE(SIN_T_FBFLAG, n, Nn)) * AreaFactor;
+            fb_tsoil += SI(VICGPU_SI_NODE(SIN_T_FBCOUNT, n, Nn));
+          }
         }
       }
       SURFT_FBFLAG += SI(SI_TSURF_FBFLAG) * AreaFactor; fb_tsurf += SI(SI_TSURF_FBCOUNT);
@@ -288,9 +295,27 @@ VIC_DEV void put_sum_part(const OArgs& a, int c) {
 #pragma unroll
       for (int l = 0; l < VIC_MAX_FRONTS; l++) { ROW(FDEPTH, l) = FDEPTH[l]; ROW(TDEPTH, l) = TDEPTH[l]; }
     }
+    if constexpr (!DEEP) {
 #pragma unroll
-    for (int n = 0; n < VIC_MAX_NODES; n++)
-      if (n < Nn) { ROW(SOIL_TNODE, n) = TNODE[n]; ROW(SOILT_FBFLAG, n) = FBNODE[n]; }
+      for (int n = 0; n < NA; n++)
+        if (n < Nn) { ROW(SOIL_TNODE, n) = TNODE[n]; ROW(SOILT_FBFLAG, n) = FBNODE[n]; }
+    } else {
+      // the same sums in the same HRU order, one node at a time (the counts are integers: their sum does not depend on the order)
+#pragma unroll 1
+      for (int n = 0; n < Nn; n++) {
+        double tn = 0, fbn = 0;
+        for (int k = k0; k < k1; k++) {
+          const int g = a.cell_list[k];
+          const PutHru h = put_hru(a, cv, g);
+          if (!h.run) continue;
+          const double AreaFactor = h.Cv * h.TreeAdjust * 1.;
+          tn += SD(VICGPU_SD_NODE(SDN_T, n, Nn)) * AreaFactor;
+          fbn += SI(VICGPU_SI_NODE(SIN_T_FBFLAG, n, Nn)) * AreaFactor;
+          fb_tsoil += SI(VICGPU_SI_NODE(SIN_T_FBCOUNT, n, Nn));
+        }
+        ROW(SOIL_TNODE, n) = tn; ROW(SOILT_FBFLAG, n) = fbn;
+      }
+    }
     ROW(SURF_FROST_FRAC, 0) = SURF_FROST_FRAC; ROW(BARESOILT, 0) = BARESOILT; ROW(VEGT, 0) = VEGT; ROW(SURF_TEMP, 0) = SURF_TEMP;
     ROW(SURFT_FBFLAG, 0) = SURFT_FBFLAG; ROW(SNOWT_FBFLAG, 0) = SNOWT_FBFLAG; ROW(TFOL_FBFLAG, 0) = TFOL_FBFLAG; ROW(TCAN_FBFLAG, 0) = TCAN_FBFLAG;
     ROW(GLAC_TSURF_FBFLAG, 0) = GLAC_TSURF_FBFLAG; ROW(NET_SHORT, 0) = NET_SHORT; ROW(NET_LONG, 0) = NET_LONG; ROW(IN_LONG, 0) = IN_LONG;
@@ -376,14 +401,17 @@ VIC_DEV void put_sum_part(const OArgs& a, int c) {
   }
 }
 
-__global__ __launch_bounds__(64) void vic_put_sum(const OArgs a) {
+template <bool DEEP>
+VIC_DEV void put_sum(const OArgs& a) {
   const int ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= a.ccount) return;
   const int c = a.c0 + ci;
-  if (blockIdx.y == 0) put_sum_part<0>(a, c);
-  else if (blockIdx.y == 1) put_sum_part<1>(a, c);
-  else put_sum_part<2>(a, c);
+  if (blockIdx.y == 0) put_sum_part<0, DEEP>(a, c);
+  else if (blockIdx.y == 1) put_sum_part<1, DEEP>(a, c);
+  else put_sum_part<2, DEEP>(a, c);
 }
+__global__ __launch_bounds__(64) void vic_put_sum(const OArgs a) { put_sum<false>(a); }          // Nnode <= VIC_MID_NODES
+__global__ __launch_bounds__(64) void vic_put_sum_deep(const OArgs a) { put_sum<true>(a); }     // Nnode > VIC_MID_NODES
 
 __global__ __launch_bounds__(64) void vic_put_finish(const OArgs a) {
   const int ci = blockIdx.x * 64 + threadIdx.x;

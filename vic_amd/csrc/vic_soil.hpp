@@ -23,7 +23,7 @@ VIC_DEV void top_layer_thermal_properties(const CellView& cv, const Soil3& s3, c
 template <int NN>
 VIC_DEV void distribute_node_moisture_properties(const Opt& o, const CellView& cv, const Soil3& s3, Nodes<NN>& nd,
                                                  const double* moist) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   int l = 0;
   bool past_bottom = false;
   double Lsum = 0.;
@@ -69,7 +69,7 @@ VIC_DEV void distribute_node_moisture_properties(const Opt& o, const CellView& c
 template <int NN>
 VIC_DEV bool estimate_layer_ice_content(const Opt& o, const CellView& cv, const Soil3& s3, const double* T,
                                         const double* moist, double* layer_ice, double* layer_T) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   // everything the layer / node walk indexes at run time is copied into small local arrays first: dynamic indexing
   // through the argument pointers would pin the caller's whole HRU struct to scratch memory
   double Lsum[4], Z[NN], Tl[NN], ml[3], mml[3], dl[3], bubl[3], exl[3], outI[3], outT[3];
@@ -152,7 +152,7 @@ VIC_DEV void estimate_layer_ice_content_quick_flux(const Opt& o, const CellView&
 // find_0_degree_fronts (soil_conduction.c:775-828)
 template <int NN>
 VIC_DEV void find_0_degree_fronts(const Opt& o, const CellView& cv, SoilEnergy& e, const double* T) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   int Nthaw = 0, Nfrost = 0;
   double td[3] = {NAN, NAN, NAN}, fd[3] = {NAN, NAN, NAN};
   for (int n = Nn - 2; n >= 0; n--) {

@@ -391,7 +391,7 @@ VIC_DEV void sf_sub_pre(const Opt& o, const CellView& cv, const VegLib& vl, cons
 template <int NN>
 VIC_DEV void sf_sub_post(const Opt& o, const CellView& cv, const VegLib& vl, const Soil3& s3, const Forcing& fc, const Dmy& dmy,
                          const StepConst& C, HruWork<NN>& w, SubLoop& L, const SubStep& P, const SurfEB& eb, const SurfSolve& sv,
-                         const double* Tprof, const int* cntprof, unsigned fbmask) {
+                         const double* Tprof, const int* cntprof, typename NodeBound<NN>::mask_t fbmask) {
   Snow& snow = w.snow;
   SnowEnergy& se = w.se;
   SoilEnergy& so = w.so;
@@ -575,7 +575,7 @@ VIC_DEV bool surface_fluxes(const Opt& o, const CellView& cv, const VegLib& vl, 
       surf_solve_consume(o, sv, eb, eb, fx);
     }
     PROF_ADD(3, t_sf);
-    sf_sub_post<NN>(o, cv, vl, s3, fc, dmy, C, w, L, P, eb, sv, nullptr, nullptr, 0u);
+    sf_sub_post<NN>(o, cv, vl, s3, fc, dmy, C, w, L, P, eb, sv, nullptr, nullptr, 0);
   } while (L.hidx < L.endhidx);
   return sf_end<NN>(o, cv, s3, C, w, L);
 }

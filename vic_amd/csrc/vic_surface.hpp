@@ -61,7 +61,7 @@ VIC_DEV void profile_node_fold(double* r, bool EXP_TRANS, bool frozen_on, double
 template <int NN>
 VIC_DEV void profile_item_store(const Opt& o, const CellView& cv, const Soil3& s3, const Nodes<NN>& nd, double deltat, bool frozen_on,
                                 double* __restrict__ blk) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   const double Dp = cv.s(CP_DP);
   const double Bexp = o.EXP_TRANS ? log(Dp + 1.) / (double)(Nn - 1) : 0.0;
 #pragma unroll
@@ -329,7 +329,7 @@ VIC_DEV void surf_setup(const Opt& o, const CellView& cv, const VegLib& vl, cons
                         const double* root, int INCLUDE_SNOW, int UnderStory, int dt, const double* lmoist, const double* lice,
                         const double* layerevap, const Nodes<NN>& nd, const SoilEnergy& e, const Snow& snow, const VegVar& vv,
                         SurfEB& eb, SurfPost& P, SurfSolve& sv) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   surf_cell_fill(eb, cv, vl, s3, fc, hidx, veg_idx, month);
   const VegMonth vm = eb.vm;
   const bool frozen_on = (cv.s(CP_FS_ACTIVE) != 0.0) && o.FROZEN_SOIL;
@@ -383,9 +383,9 @@ struct SurfOut { double Tsurf, melt, ppt; bool ok; };
 // profile of the final evaluation (unused with QUICK_FLUX).  lice/lT: layer ice and temperature out.
 template <int NN>
 VIC_DEV SurfOut surf_post(const Opt& o, const CellView& cv, const Soil3& s3, const SurfPost& P, const SurfEB& eb, const SurfSolve& sv,
-                          const double* Tprof, const int* cntprof, unsigned fbmask, const double* lmoist, double* lice, double* lT,
+                          const double* Tprof, const int* cntprof, typename NodeBound<NN>::mask_t fbmask, const double* lmoist, double* lice, double* lT,
                           double* layerevap, double* ra_used, Nodes<NN>& nd, SoilEnergy& e, Snow& snow, VegVar& vv) {
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   SurfOut out;
   out.ok = sv.ok != 0; out.melt = P.melt_in; out.ppt = P.ppt_in;
   const double Tsurf = sv.Tsurf;
@@ -487,7 +487,7 @@ VIC_DEV SurfOut surf_post(const Opt& o, const CellView& cv, const Soil3& s3, con
   e.Tsurf_fbflag = sv.fbflag;
   e.Tsurf_fbcount += sv.fbcount;
 #pragma unroll
-  for (int n = 0; n < NN; n++) { nd.fbflag[n] = (fbmask >> n) & 1u; nd.fbcount[n] += cntnew[n]; }
+  for (int n = 0; n < NN; n++) { nd.fbflag[n] = (int)((fbmask >> n) & 1u); nd.fbcount[n] += cntnew[n]; }
   out.Tsurf = Tsurf;
   return out;
 }

@@ -21,6 +21,27 @@
 
 namespace vic {
 
+// ---- node-count instantiations: the FD kernels exist for exactly 10 nodes and for two generic bounds, VIC_MID_NODES
+// (any other count up to 24, IMPLICIT's range) and VIC_MAX_NODES (25 .. 50).  A generic instantiation runs o.Nnode nodes.
+constexpr int VIC_MID_NODES = 24;
+static_assert(VIC_MID_NODES < VIC_MAX_NODES && VIC_MAX_NODES <= 63, "node bounds");
+template <bool B, class T, class F> struct vic_cond { using type = T; };
+template <class T, class F> struct vic_cond<false, T, F> { using type = F; };
+// the instantiation a node count runs on
+__host__ __device__ constexpr int node_bound(int Nnode) { return Nnode == 10 ? 10 : (Nnode <= VIC_MID_NODES ? VIC_MID_NODES : VIC_MAX_NODES); }
+// the bit of a profile solution record's flag word that holds `ok`: the one above the fall-back mask of the bound
+// (vic_profile.hpp; read at run time by vic_surf_eval through node_bound)
+__host__ __device__ constexpr int record_ok_bit(int bound) { return bound > 32 ? 63 : 32; }
+template <int NN> struct NodeBound {
+  static constexpr bool generic = (NN == VIC_MID_NODES || NN == VIC_MAX_NODES);
+  // per-node fall-back flags of one profile solve: 32 bits while they fit (the <= 24-node kernels are unchanged by the
+  // deep bound), 64 bits above
+  using mask_t = typename vic_cond<(NN > 32), unsigned long long, unsigned>::type;
+  static constexpr int ok_bit = record_ok_bit(NN);
+  static_assert(ok_bit >= 8 * (int)sizeof(mask_t) || NN < ok_bit, "ok bit above every node's flag");
+};
+template <int NN> VIC_DEV constexpr int node_count(int Nnode) { return NodeBound<NN>::generic ? Nnode : NN; }
+
 // ---- constants shared with the reference (vicNl_def.h:138-302, snow.h:34-79) ----
 constexpr double ERROR_VAL = -999.0;
 constexpr double HUGE_RESIST = 1.e20;

@@ -693,7 +693,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
   VegLib vl{a.veglib};
   Forcing fc{a.forcing, a.snowflag, a.ncell, id.c, o.NR + 1};
   const Soil3 s3 = load_soil3(cv);
-  const int Nn = (NN == VIC_MAX_NODES) ? o.Nnode : NN;
+  const int Nn = node_count<NN>(o.Nnode);
   const CtxRef cx = CtxRef::at(a.ctx, ctx_words<NN>(), g);
   HruWork<NN> w;
   StepConst C;
@@ -753,7 +753,9 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
       Tprof[n] = (n < Nn) ? po[n] : 0.0;
       cntprof[n] = (n < Nn) ? poc[n] : 0;
     }
-    sf_sub_post<NN>(o, cv, vl, s3, fc, a.dmy, C, w, L, P, eb, sv, Tprof, cntprof, (unsigned)(flags & 0xFFFFFFFFull));
+    using mask_t = typename NodeBound<NN>::mask_t;      // the flag bits below the record's ok bit
+    sf_sub_post<NN>(o, cv, vl, s3, fc, a.dmy, C, w, L, P, eb, sv, Tprof, cntprof,
+                    (mask_t)(flags & ((1ull << NodeBound<NN>::ok_bit) - 1ull)));
     PROF_ADD(12, t_post);
     more = true;
   }
@@ -806,6 +808,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
             if (w.nd.T[n] < 0) nfrozen++;
             if (fabs(w.nd.T[n]) < SOIL_DT) kink = true;
           }
+        if constexpr (NN >= NBUCKET / 2) nfrozen = (nfrozen < NBUCKET / 2 - 1) ? nfrozen : NBUCKET / 2 - 1;    // deep bound: 25+ share the top segment
         key = nfrozen + (kink ? NBUCKET / 2 : 0);
         a.hkey[g] = key;
       }
@@ -960,7 +963,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void v
   }
   const double* __restrict__ rec = a.pout + (size_t)g * pout_hru_stride(a.Nn);
   const double* __restrict__ po = rec + slot * pout_stride(a.Nn);
-  const bool ok = (((unsigned long long)__double_as_longlong(po[a.Nn])) >> 32) & 1ull;
+  const bool ok = (((unsigned long long)__double_as_longlong(po[a.Nn])) >> record_ok_bit(node_bound(a.Nn))) & 1ull;
   if (sv.stage == SurfSolve::FINAL) sv.final_slot = slot;
   const double fx = ok ? eb.eval(a.o, s3, sv.x, po[1], po[2]) : ERROR_VAL;
   const bool was_quick = sv.stage == SurfSolve::ROOT_QUICK;
@@ -1442,7 +1445,7 @@ static hipError_t launch_fd_stage(const KArgs& ka, bool multi, hipStream_t st) {
   return hipGetLastError();
 }
 
-// The profile kernel of a node count: 10 nodes have the register-resident instantiation, every other count the generic one
+// The profile kernel of a node count: 10 nodes have the register-resident instantiation, every other count a generic one
 template <int NN>
 static hipError_t launch_profile(const PArgs& pa, int nmax, int resident_waves, bool newton, hipStream_t st) {
   int nblk = (nmax + 63) / 64;
@@ -1502,22 +1505,26 @@ static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* nevalonly) {
   return VICGPU_OK;
 }
 
+// F<NN>(args) for the instantiation node count Nnode runs on (node_bound: 10, VIC_MID_NODES or VIC_MAX_NODES)
+#define NODE_DISPATCH(Nnode, F, ...)                                                                                          \
+  (node_bound(Nnode) == 10 ? F<10>(__VA_ARGS__)                                                                           \
+                           : node_bound(Nnode) == VIC_MID_NODES ? F<VIC_MID_NODES>(__VA_ARGS__) : F<VIC_MAX_NODES>(__VA_ARGS__))
+
 static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
   const int Nn = c->o.Nnode;
-  const bool n10 = (Nn == 10);
   hipStream_t st = ch->stream;
-  if (c->any_glacier) CHKCH(ch, (n10 ? launch_hru<10>(ka, st, false, true) : launch_hru<VIC_MAX_NODES>(ka, st, false, true)));
+  if (c->any_glacier) CHKCH(ch, NODE_DISPATCH(Nn, launch_hru, ka, st, false, true));
   CHKCH(ch, hipMemsetAsync(ch->d_count, 0, sizeof(int) * CNT_TOTAL, st));
   int cur = 0;
   ka.phase = 0; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur); ka.list_cap = ch->list_cap;
-  CHKCH(ch, (n10 ? launch_fd_stage<10>(ka, c->o.NF > 1, st) : launch_fd_stage<VIC_MAX_NODES>(ka, c->o.NF > 1, st)));
+  CHKCH(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
   PArgs pa;
   pa.pin = c->d_pin; pa.ts = c->d_ts; pa.pout = c->d_pout; pa.pslot = c->d_pslot; pa.Nn = Nn; pa.NOFLUX = c->o.NOFLUX; pa.EXP_TRANS = c->o.EXP_TRANS;
   pa.TFALLBACK = c->o.TFALLBACK; pa.next = ch->d_count + CNT_CURSOR; pa.cap = ch->list_cap; pa.jl = c->d_jl;
   EArgs ea;
   ea.o = c->o; ea.ncell = c->ncell; ea.nhru = c->nhru; ea.Nn = Nn; ea.glist = ch->d_glist; ea.gcount = ch->gcount; ea.map = ch->map;
   ea.cell_params = c->d_cp; ea.hpi = c->d_hpi; ea.ctx = c->d_ctx;
-  ea.ctx_words = n10 ? ctx_words<10>() : ctx_words<VIC_MAX_NODES>();
+  ea.ctx_words = NODE_DISPATCH(Nn, ctx_words);
   ea.pout = c->d_pout; ea.pslot = c->d_pslot; ea.ts = c->d_ts; ea.hstate = c->d_hstate; ea.profile_next = ch->d_count + CNT_CURSOR;
   ea.list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
   ea.list_cap = ch->list_cap; ea.hkey = c->d_hkey; ea.implicit = c->o.IMPLICIT; ea.jl = c->d_jl;
@@ -1551,8 +1558,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
         CHKCH(ch, hipGetLastError());
         pa.list = ch->d_fb_list; pa.count = ch->d_fb_count;
       }
-      CHKCH(ch, (n10 ? launch_profile<10>(pa, nmax, c->profile_waves, c->node_newton, st)
-                     : launch_profile<VIC_MAX_NODES>(pa, nmax, c->profile_waves, c->node_newton, st)));
+      CHKCH(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
       ea.list_next = ch->d_list[cur ^ 1]; ea.count_next = cnt_list(ch->d_count, cur ^ 1);
       ea.evalonly = cnt_evalonly(ch->d_count, cur ^ 1); ea.eo_list_next = ch->d_elist[cur ^ 1];
       ea.list_cur = ch->d_list[cur]; ea.count_cur = cnt_list(ch->d_count, cur);
@@ -1591,7 +1597,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       }
     }
     ka.phase = p; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur);
-    CHKCH(ch, (n10 ? launch_fd_stage<10>(ka, c->o.NF > 1, st) : launch_fd_stage<VIC_MAX_NODES>(ka, c->o.NF > 1, st)));
+    CHKCH(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
     if (p < nsub) {
       int n = 0, ne = 0;
       const int r = fd_read_count(ch, cur, &n, &ne);
@@ -1615,7 +1621,8 @@ static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, i
   const unsigned nblk = (unsigned)((ccount + 63) / 64);
   // zero_output_list: the columns of these cells in every row
   hipLaunchKernelGGL(vic_put_zero, dim3(nblk, (c->out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(vic_put_sum, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
+  if (c->o.Nnode > VIC_MID_NODES) hipLaunchKernelGGL(vic_put_sum_deep, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL(vic_put_sum, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
   hipLaunchKernelGGL(vic_put_finish, dim3(nblk), dim3(64), 0, st, a);
   if (s >= 0)
     hipLaunchKernelGGL(vic_put_aggregate, dim3(nblk, (c->out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a, c->d_rowagg);
@@ -1699,6 +1706,8 @@ int vicgpu_create(const vicgpu_options* opt, int device, vicgpu_ctx** out) {
   // NOFLUX and EXP_TRANS off for the iteration and keeps whatever it last set for the final evaluation (NOFLUX returns with a
   // second iteration, EXP_TRANS never does): reproduced; not combined with IMPLICIT
   if (opt->QUICK_SOLVE && !opt->QUICK_FLUX && opt->IMPLICIT) return VICGPU_ERR_UNSUPPORTED;
+  // IMPLICIT up to VIC_MID_NODES nodes (the reference's own Newton-Raphson solver stops at 21: MAXSIZE, newt_raph_func_fast.c:7)
+  if (opt->IMPLICIT && !opt->QUICK_FLUX && opt->Nnode > VIC_MID_NODES) return VICGPU_ERR_UNSUPPORTED;
   // IMPLICIT (newt_raph_func_fast.c): the finite-difference soil profile with the node freezing parameters of the node
   // arrays; the reference as shipped reads the 3-element layer arrays out of bounds there (frozen_soil.c:283-284)
   if (opt->IMPLICIT && (opt->QUICK_FLUX || opt->frozen_compat)) return VICGPU_ERR_UNSUPPORTED;
@@ -1843,7 +1852,7 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
   c->fd = !c->o.QUICK_FLUX;
   if (c->fd) {
     const int Nn = c->o.Nnode;
-    const size_t words = (Nn == 10) ? ctx_words<10>() : ctx_words<VIC_MAX_NODES>();
+    const size_t words = NODE_DISPATCH(Nn, ctx_words);
     HIPCHK(c, hipMalloc(&c->d_ctx, sizeof(unsigned long long) * ctx_padded_words(words) * (((size_t)nhru + 63) / 64 * 64)));
     HIPCHK(c, hipMalloc(&c->d_pin, sizeof(double) * (size_t)Nn * PREC * nhru));
     HIPCHK(c, hipMalloc(&c->d_ts, sizeof(double) * nhru));
@@ -1869,8 +1878,7 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
     // frozen-node root finder (vic_profile.hpp): the option, overridable for A/B runs
     c->node_newton = c->opt.NODE_SOLVER == VIC_NODE_SOLVER_NEWTON;
     if (const char* ev = getenv("VICGPU_NODE_SOLVER")) c->node_newton = (strcmp(ev, "newton") == 0);
-    c->profile_waves = (Nn == 10) ? profile_resident_waves<10>(c->device, c->node_newton)
-                                  : profile_resident_waves<VIC_MAX_NODES>(c->device, c->node_newton);
+    c->profile_waves = NODE_DISPATCH(Nn, profile_resident_waves, c->device, c->node_newton);
     // tuning: the pending share (percent of the chunk's HRUs) from which the evaluation rounds run from the pending list; 0 = never
     if (const char* ev = getenv("VICGPU_EVAL_LIST_PCT")) {
       const int pct = atoi(ev);

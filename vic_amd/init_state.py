@@ -177,10 +177,14 @@ def initial_state(dom, forcing0):
             return uy + (ly - uy) * np.exp(-(x - lx))
         T[0] = surf_temp
         T[Nn - 1] = avg_temp
-        T[1] = exp_interp(depth[0], 0., dp, surf_temp, avg_temp)
-        T[2] = exp_interp(2. * depth[0], 0., dp, surf_temp, avg_temp)
-        for n in range(3, Nn - 1):
-            T[n] = exp_interp(Z[n], 0., dp, surf_temp, avg_temp)
+        if opt.EXP_TRANS:                                            # initialize_model_state.c:622-633: middle nodes at their own depths
+            for n in range(1, Nn - 1):
+                T[n] = exp_interp(Z[n], 0., dp, surf_temp, avg_temp)
+        else:                                                        # initialize_model_state.c:561-586
+            T[1] = exp_interp(depth[0], 0., dp, surf_temp, avg_temp)
+            T[2] = exp_interp(2. * depth[0], 0., dp, surf_temp, avg_temp)
+            for n in range(3, Nn - 1):
+                T[n] = exp_interp(Z[n], 0., dp, surf_temp, avg_temp)
     mo, ic, ka, cs = distribute_node_moisture_properties(opt, cp, cell, T, moist)
     if opt.QUICK_FLUX:
         lice, lT = estimate_layer_ice_content_quick_flux(opt, cp, cell, T[0], T[1], moist)
