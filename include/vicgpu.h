@@ -464,6 +464,21 @@ enum { VICGPU_NODE_NODE1 = 1, VICGPU_NODE_NEWTON = 2, VICGPU_NODE_EXP_TRANS = 4 
 #define VICGPU_NODE_NOUT 2
 int   vicgpu_debug_node_root(vicgpu_ctx *ctx, int mode, int n, const double *in, double *out);
 
+/* ---- test hook: replay a recorded root find -------------------------------------
+ * The model's root finders (vic_math.hpp) for n independent cases, one lane each:
+ * mode 0 Brent (the surface, snow, canopy and glacier solves), mode 1 BrentLean (the
+ * frozen-node visits).  Lane i starts from bounds[i][0], bounds[i][1]; at its k-th
+ * residual request it writes the abscissa to xreq[off[i] + k] and is given
+ * fvals[off[i] + k] instead of a residual evaluation.  off: int[n + 1], off[0] = 0,
+ * non-decreasing; fvals and xreq hold off[n] values.
+ * out: double[n][VICGPU_BRENT_NOUT]: values consumed, finished, failed, result (ERROR
+ * on failure), the counters i, j, k, which_err (BrentLean: k = which_err = 0), and
+ * overrun (1: the lane asked for more values than off[i + 1] - off[i]). */
+enum { VICGPU_BRENT_FULL = 0, VICGPU_BRENT_LEAN = 1 };
+#define VICGPU_BRENT_NOUT 9
+int   vicgpu_debug_root_brent(vicgpu_ctx *ctx, int mode, int n, const double *bounds, const int *off, const double *fvals,
+                              double *xreq, double *out);
+
 /* GPU time (ms) per model step of the last vicgpu_step call, measured with
  * hipEvents on the library's streams: QUICK_FLUX: the step's HRU kernel, one
  * event pair per step; finite-difference pipeline: all kernels of all steps

@@ -204,6 +204,15 @@ double orc_stability_correction(double Z, double d, double TSurf, double Tair, d
 typedef double (*orc_fn)(double x, void *ctx);
 double orc_root_brent(double lower, double upper, orc_fn f, void *ctx);
 double orc_root_brent_tol(double lower, double upper, orc_fn f, void *ctx, double MACHEPS, double TTOL);
+/* test hook (tests/brent_cases.py records real root finds with it): when set, called after every residual evaluation of
+ * orc_root_brent_tol with the solve's running number (root finds nest: the surface residual runs node solves, whose
+ * evaluations are recorded before the surface one that contains them), the residual, the bounds and tolerances, the
+ * evaluation's index k within the solve, x and f(x).  NULL in every model run; only vicorc_set_brent_recorder sets it,
+ * for single-threaded runs. */
+typedef void (*orc_brent_rec)(int solve, orc_fn fn, double lower, double upper, double MACHEPS, double TTOL, int k, double x,
+                              double fx, void *rctx);
+void vicorc_set_brent_recorder(orc_brent_rec rec, void *rctx);
+orc_fn vicorc_node_residual(void);         /* the frozen-node residual (soil_thermal_eqn.c), to tell its solves apart */
 double orc_calc_veg_height(double displacement, double L);
 int    orc_calc_aerodynamic(int overstory, double height, double trunk, double z0_snow, double z0_soil, double n,
                             orc_vc *aero_resist, orc_vc *wind_speed, orc_vc *displacement, orc_vc *ref_height, orc_vc *roughness);

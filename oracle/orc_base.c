@@ -77,12 +77,27 @@ double orc_root_brent(double lower, double upper, orc_fn f, void *ctx) {
   return orc_root_brent_tol(lower, upper, f, ctx, 3e-8, 1e-7);                      /* root_brent.c:32-36 */
 }
 
-double orc_root_brent_tol(double lower, double upper, orc_fn f, void *ctx, double MACHEPS, double TTOL) {
+static orc_brent_rec brent_rec = NULL;
+static void *brent_rec_ctx = NULL;
+static int brent_solves = 0;
+void vicorc_set_brent_recorder(orc_brent_rec rec, void *rctx) { brent_rec = rec; brent_rec_ctx = rctx; brent_solves = 0; }
+
+static double brent_eval(orc_fn f, void *ctx, double x, double lower, double upper, double MACHEPS, double TTOL, int solve,
+                         int *nev) {
+  const double fx = f(x, ctx);
+  if (brent_rec) brent_rec(solve, f, lower, upper, MACHEPS, TTOL, *nev, x, fx, brent_rec_ctx);
+  (*nev)++;
+  return fx;
+}
+
+double orc_root_brent_tol(double lower, double upper, orc_fn fn, void *ctx, double MACHEPS, double TTOL) {
   const int MAXTRIES = 5, MAXITER = 1000;
   const double TSTEP = 10;
   double a = lower, b = upper, c = 0, d = 0, e = 0, fa, fb, fc, m, p, q, r, s, tol;
   double last_bad = 0, last_good = 0;
-  int which_err = 0, i, j;
+  int which_err = 0, i, j, nev = 0;
+  const int solve = brent_rec ? brent_solves++ : 0;
+#define f(x, ctx) brent_eval(fn, ctx, x, lower, upper, MACHEPS, TTOL, solve, &nev)     /* every residual call passes the recorder */
 
   fa = f(a, ctx);
   fb = f(b, ctx);
@@ -160,6 +175,7 @@ double orc_root_brent_tol(double lower, double upper, orc_fn f, void *ctx, doubl
     if (fb == ORC_ERROR) return ORC_ERROR;
   }
   return ORC_ERROR;
+#undef f
 }
 
 /* ------------------------------------------------------------------ aerodynamics */

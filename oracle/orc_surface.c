@@ -743,3 +743,6 @@ double orc_estimate_T1_x(double Ts, double T1_old, double T2, double D1, double 
                          double dp, double delta_t) {
   return orc_estimate_T1(Ts, T1_old, T2, D1, D2, kappa1, kappa2, Cs1, Cs2, dp, delta_t);
 }
+
+/* test hook: the node residual's address, for the root-find recorder (orc.h) */
+orc_fn vicorc_node_residual(void) { return orc_soil_thermal_eqn; }

@@ -370,3 +370,49 @@ def have_ref(variant="plain"):
 
 def have_oracle():
     return os.path.exists(oracle_lib_path())
+
+
+_BRENT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_double, ctypes.c_void_p)
+
+
+def _recording(f):
+    """A ctypes residual that calls f and records (xs, fs)."""
+    xs, fs = [], []
+
+    def cb(x, _):
+        v = float(f(x))
+        xs.append(x)
+        fs.append(v)
+        return v
+    return _BRENT_FN(cb), xs, fs
+
+
+def ref_root_brent(lower, upper, f, variant="plain"):
+    """The reference's RootBrent::root_brent (root_brent.c:97-337) on the Python residual f, through vicref_root_brent.
+    Returns (result, xs, fs, error string): the abscissae requested in order and the values returned."""
+    lib = ctypes.CDLL(ref_lib_path(variant), mode=os.RTLD_LAZY)
+    fn = lib.vicref_root_brent
+    fn.restype = ctypes.c_double
+    fn.argtypes = [ctypes.c_double, ctypes.c_double, _BRENT_FN, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+    cb, xs, fs = _recording(f)
+    err = ctypes.create_string_buffer(2048)
+    r = fn(float(lower), float(upper), cb, None, err, len(err))
+    return r, xs, fs, err.value.decode()
+
+
+def oracle_root_brent(lower, upper, f, macheps=None, ttol=None):
+    """The oracle's orc_root_brent (orc_root_brent_tol when the node tolerances are given) on the Python residual f.
+    Returns (result, xs, fs)."""
+    lib = ctypes.CDLL(oracle_lib_path())
+    cb, xs, fs = _recording(f)
+    if macheps is None:
+        fn = lib.orc_root_brent
+        fn.restype = ctypes.c_double
+        fn.argtypes = [ctypes.c_double, ctypes.c_double, _BRENT_FN, ctypes.c_void_p]
+        r = fn(float(lower), float(upper), cb, None)
+    else:
+        fn = lib.orc_root_brent_tol
+        fn.restype = ctypes.c_double
+        fn.argtypes = [ctypes.c_double, ctypes.c_double, _BRENT_FN, ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
+        r = fn(float(lower), float(upper), cb, None, float(macheps), float(ttol))
+    return r, xs, fs

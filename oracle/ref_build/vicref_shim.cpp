@@ -771,6 +771,24 @@ int vicref_derive_forcing(void *hv, int nsteps, int force_dt, const double *file
   return 0;
 }
 
+/* the reference's RootBrent::root_brent (root_brent.c:97-337) on a residual supplied by the caller: a subclass whose
+ * calculate(x) calls cb(x, ctx).  Returns the reference's result; its error string (empty on success) goes to err. */
+class VicrefCallbackBrent : public RootBrent {
+public:
+  double (*cb)(double, void *);
+  void *ctx;
+  VicrefCallbackBrent(double (*f)(double, void *), void *c) : cb(f), ctx(c) {}
+  double calculate(double x) override { return cb(x, ctx); }
+};
+
+double vicref_root_brent(double lower, double upper, double (*cb)(double, void *), void *ctx, char *err, int errlen) {
+  char buf[2048] = {0};
+  VicrefCallbackBrent rb(cb, ctx);
+  const double r = rb.root_brent(lower, upper, buf);
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", buf);
+  return r;
+}
+
 int vicref_max_threads(void) {
 #ifdef _OPENMP
   return omp_get_max_threads();

@@ -11,7 +11,8 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def golden_names():
     names = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
-    return [n for n in names if not n.startswith(("pure_", "gmb_", "forcing_derive_"))]      # pure_*.npz: per-function vectors, tests/pure_inputs.py
+    # pure_*.npz: per-function vectors, tests/pure_inputs.py; brent_*.npz: root-finder traces, tests/test_brent.py
+    return [n for n in names if not n.startswith(("pure_", "gmb_", "forcing_derive_", "brent_"))]
 
 
 def load_golden(name):

@@ -72,3 +72,10 @@ def test_node_root_battery_clean(hostemu_lib):
     violated bound."""
     out = _run(*hostemu_lib, [], False, script="check_node_root.py")
     assert out.count(" 0 violations;") == 2, out
+
+
+def test_brent_battery_clean(hostemu_lib):
+    """The Brent battery of tests/test_brent.py (tests/golden/brent_traces.npz) through vicgpu_debug_root_brent: Brent's
+    replay bit for bit, BrentLean's up to its documented difference (tools/hostemu/check_brent.py)."""
+    out = _run(*hostemu_lib, [], False, script="check_brent.py")
+    assert out.count(" 0 problems") == 2, out

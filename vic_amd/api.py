@@ -63,6 +63,7 @@ def load_library():
         "vicgpu_last_kernel_ms": (ctypes.c_int, [vp, _dp, _ip]),
         "vicgpu_debug_pure": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
         "vicgpu_debug_node_root": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+        "vicgpu_debug_root_brent": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _ip, _dp, _dp, _dp]),
         "vicgpu_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
         "vicgpu_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
@@ -135,7 +136,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_state", "vicgpu_get_state", "vicgpu_push_forcing", "vicgpu_step", "vicgpu_synchronize", "vicgpu_get_fluxes",
     "vicgpu_get_cell_outputs", "vicgpu_get_accum", "vicgpu_reset_accum", "vicgpu_get_cell_errors", "vicgpu_set_stream",
     "vicgpu_set_write_fluxes", "vicgpu_device_ptr", "vicgpu_last_kernel_ms", "vicgpu_debug_pure",
-    "vicgpu_debug_node_root", "vicgpu_glacier_mass_balance_fit",
+    "vicgpu_debug_node_root", "vicgpu_debug_root_brent", "vicgpu_glacier_mass_balance_fit",
     "vicgpu_out_nvar", "vicgpu_out_var_id", "vicgpu_out_var_name", "vicgpu_out_var_kind", "vicgpu_out_var_agg", "vicgpu_out_var_nelem",
     "vicgpu_put_data_config", "vicgpu_put_data_init", "vicgpu_get_outputs", "vicgpu_get_output_data", "vicgpu_get_balance",
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
@@ -369,6 +370,20 @@ class Model:
         out = np.zeros((inp.shape[0], C["VICGPU_NODE_NOUT"]))
         self._chk(self.lib.vicgpu_debug_node_root(self.h, int(mode), inp.shape[0], _d(inp), _d(out)))
         return out[:, 0].copy(), out[:, 1] != 0
+
+    def debug_root_brent(self, mode, bounds, fvals, off):
+        """Test hook (vicgpu_debug_root_brent): replays root finds with recorded residual values.  bounds [n][2]; case i is
+        given fvals[off[i]:off[i + 1]] in turn; mode VICGPU_BRENT_FULL (Brent) or VICGPU_BRENT_LEAN (BrentLean).
+        Returns (xreq [off[n]]: the abscissae requested, out [n][VICGPU_BRENT_NOUT])."""
+        b = np.ascontiguousarray(bounds, dtype=np.float64)
+        f = np.ascontiguousarray(fvals, dtype=np.float64)
+        o = np.ascontiguousarray(off, dtype=np.int32)
+        assert b.ndim == 2 and b.shape[1] == 2 and b.shape[0] > 0 and o.shape == (b.shape[0] + 1,) and f.shape == (o[-1],)
+        x = np.full(max(int(o[-1]), 1), np.nan)
+        out = np.zeros((b.shape[0], C["VICGPU_BRENT_NOUT"]))
+        self._chk(self.lib.vicgpu_debug_root_brent(self.h, int(mode), b.shape[0], _d(b), _i(o), _d(f) if f.size else None,
+                                                   _d(x), _d(out)))
+        return x[:o[-1]].copy(), out
 
     def last_kernel_ms(self):
         ms = ctypes.c_double(0)

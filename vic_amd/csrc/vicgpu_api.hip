@@ -1201,6 +1201,44 @@ __global__ __launch_bounds__(64) void vic_debug_node_root(const NRArgs d) {
   }
 }
 
+// One root find per lane (vicgpu_debug_root_brent): the production state machines, fed with recorded residual values.
+// The lanes of a wave loop until the last one is done, as in the solves of the model.
+struct RBArgs { int n; const double* bounds; const int* off; const double* fvals; double* xreq; double* out; };
+
+__device__ __forceinline__ bool rb_finished(const Brent& st) { return st.phase == Brent::DONE; }
+__device__ __forceinline__ bool rb_finished(const BrentLean& st) { return st.finished(); }
+// out[2..7]: failed, result, i, j, k, which_err.  Brent's only failure mark is its ERROR result (root_brent.c's return value).
+__device__ __forceinline__ void rb_report(const Brent& st, double* r) {
+  r[2] = (st.phase == Brent::DONE && st.result == ERROR_VAL) ? 1.0 : 0.0;
+  r[3] = st.result; r[4] = st.i; r[5] = st.j; r[6] = st.k; r[7] = st.which_err;
+}
+__device__ __forceinline__ void rb_report(const BrentLean& st, double* r) {
+  r[2] = (st.phase == BrentLean::FAILED) ? 1.0 : 0.0;
+  r[3] = (st.phase == BrentLean::DONE) ? st.b : ERROR_VAL; r[4] = st.i; r[5] = st.j; r[6] = 0; r[7] = 0;
+}
+
+template <class S>
+__global__ __launch_bounds__(64) void vic_debug_root_brent(const RBArgs d) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= d.n) return;
+  const int o0 = d.off[i], o1 = d.off[i + 1];
+  S st;
+  st.start(d.bounds[2 * (size_t)i], d.bounds[2 * (size_t)i + 1]);
+  int k = 0;
+  bool overrun = false;
+  while (!rb_finished(st)) {
+    if (o0 + k >= o1) { overrun = true; break; }
+    d.xreq[o0 + k] = st.x;
+    st.advance(d.fvals[o0 + k]);
+    k++;
+  }
+  double* r = d.out + (size_t)i * VICGPU_BRENT_NOUT;
+  r[0] = k;
+  r[1] = rb_finished(st) ? 1.0 : 0.0;
+  rb_report(st, r);
+  r[8] = overrun ? 1.0 : 0.0;
+}
+
 // ------------------------------------------------------------------------------------------------ cell kernel
 struct CArgs {
   int ncell, nhru;
@@ -2320,6 +2358,41 @@ int vicgpu_debug_pure(vicgpu_ctx* c, int fn, int n, const double* in, double* ou
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
   HIPIGN(hipFree(d_in)); HIPIGN(hipFree(d_out));
+  HIPCHK(c, e);
+  return VICGPU_OK;
+}
+
+int vicgpu_debug_root_brent(vicgpu_ctx* c, int mode, int n, const double* bounds, const int* off, const double* fvals,
+                            double* xreq, double* out) {
+  if (!c || (mode != VICGPU_BRENT_FULL && mode != VICGPU_BRENT_LEAN) || n <= 0 || !bounds || !off || !out) return VICGPU_ERR_ARG;
+  if (off[0] != 0) return VICGPU_ERR_ARG;
+  for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) return VICGPU_ERR_ARG;
+  const int nv = off[n];
+  if (nv > 0 && (!fvals || !xreq)) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  double *d_bounds = nullptr, *d_f = nullptr, *d_x = nullptr, *d_out = nullptr;
+  int* d_off = nullptr;
+  const size_t nvs = nv > 0 ? (size_t)nv : 1;
+  hipError_t e = hipMalloc(&d_bounds, sizeof(double) * 2 * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&d_off, sizeof(int) * ((size_t)n + 1));
+  if (e == hipSuccess) e = hipMalloc(&d_f, sizeof(double) * nvs);
+  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * nvs);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT);
+  if (e == hipSuccess) e = copy_on(c->stream, d_bounds, bounds, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = copy_on(c->stream, d_off, off, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice);
+  if (e == hipSuccess && nv > 0) e = copy_on(c->stream, d_f, fvals, sizeof(double) * (size_t)nv, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    RBArgs d;
+    d.n = n; d.bounds = d_bounds; d.off = d_off; d.fvals = d_f; d.xreq = d_x; d.out = d_out;
+    const dim3 grid((n + 63) / 64), block(64);
+    if (mode == VICGPU_BRENT_FULL) hipLaunchKernelGGL((vic_debug_root_brent<Brent>), grid, block, 0, c->stream, d);
+    else hipLaunchKernelGGL((vic_debug_root_brent<BrentLean>), grid, block, 0, c->stream, d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && nv > 0) e = copy_on(c->stream, xreq, d_x, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT, hipMemcpyDeviceToHost);
+  HIPIGN(hipFree(d_bounds)); HIPIGN(hipFree(d_off)); HIPIGN(hipFree(d_f)); HIPIGN(hipFree(d_x)); HIPIGN(hipFree(d_out));
   HIPCHK(c, e);
   return VICGPU_OK;
 }
