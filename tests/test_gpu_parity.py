@@ -405,6 +405,40 @@ def test_chunking_is_invisible(monkeypatch):
         assert np.array_equal(a, b, equal_nan=True)
 
 
+def test_second_domain_on_one_context(monkeypatch):
+    """vicgpu_set_domain on a handle that already has a domain: the first domain's tables, chunks, outputs and forcing go,
+    and what the handle computes from there on is, bit for bit, what a fresh context computes on the second domain.  The
+    first domain is 70 cells x 2 tiles x 2 bands in two chunks of 35 cells (less than a wave per slot: ragged last waves),
+    the second one 6 cells."""
+    from vic_amd.api import Model
+    monkeypatch.setenv("VICGPU_CHUNKS", "2")
+    kw, _, ntile, doy = CASES["glacier_frozen"]
+    first = _setup(kw, 70, ntile, 2, doy)
+    d, f, sf, dmy, sd0, si0 = _setup(kw, 6, ntile, 3, doy)
+
+    def run(m):
+        m.set_state(sd0, si0)
+        m.push_forcing(f, sf, dmy)
+        m.dist_prec(0, 2)
+        r = [*m.get_state(), m.get_fluxes(), m.get_cell_errors()]
+        m.put_data_config(1); m.put_data_init()
+        m.dist_prec(2, 1)
+        names = [t[0] for t in m.output_list()]
+        return r + [m.get_outputs(names, reset=False), m.get_output_data(names)]
+    m = Model(first[0])
+    m.set_state(*first[4:])
+    m.push_forcing(*first[1:4])
+    m.put_data_config(1); m.put_data_init()
+    m.dist_prec(0, 2)
+    assert m.get_cell_errors().sum() == 0
+    m.set_domain(d)
+    got = run(m)
+    want = run(Model(d))
+    assert len(got) == len(want) == 6
+    for a, b in zip(want, got):
+        assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+
+
 @pytest.mark.parametrize("case", ["frozen_fixed", "frozen_wb_daily"])
 def test_launch_shapes_are_invisible(monkeypatch, case):
     """How the evaluation rounds are launched is tuning, not physics: dense rounds in XCD-aware block order or in plain order,

@@ -79,3 +79,20 @@ def test_brent_battery_clean(hostemu_lib):
     replay bit for bit, BrentLean's up to its documented difference (tools/hostemu/check_brent.py)."""
     out = _run(*hostemu_lib, [], False, script="check_brent.py")
     assert out.count(" 0 problems") == 2, out
+
+
+def test_lifecycle_leaves_nothing_behind(hostemu_lib):
+    """Every runtime object the host layer creates has one owner (vic_amd/csrc/vic_host.hpp): per option set, the read-backs
+    leave the object count alone, a second vicgpu_set_domain on the same handle computes what a fresh context does, and
+    after close the count is back where it was before create (tools/hostemu/check_lifecycle.py)."""
+    out = _run(*hostemu_lib, ["lifecycle"], False, script="check_lifecycle.py")
+    assert out.count(" 0 left after close, second domain differs in: nothing") == 3, out
+    assert "check_lifecycle lifecycle: 0 problems" in out, out
+
+
+def test_refused_allocations_leave_nothing_behind(hostemu_lib):
+    """Every entry point that allocates, with the n-th allocation refused for every n it makes: VICGPU_ERR_HIP, the object
+    count where it was, and the first call that gets through computes what an undisturbed context computes."""
+    out = _run(*hostemu_lib, ["refusals"], False, script="check_lifecycle.py")
+    assert out.count(" refused, then through") == 13, out
+    assert "check_lifecycle refusals: 0 problems" in out, out

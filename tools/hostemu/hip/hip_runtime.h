@@ -188,6 +188,10 @@ inline void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
 // runtime objects alive (device and pinned allocations, streams, events): a failed call that leaves one behind shows up here
 inline std::atomic<long long> live_objects{0};
 
+// checker hook (hostemu_refuse_alloc below): the allocation that brings the countdown to zero fails like one the runtime refuses
+inline std::atomic<long long> refuse_countdown{0};
+inline bool refuse_alloc() { return refuse_countdown.load() > 0 && refuse_countdown.fetch_sub(1) == 1; }
+
 // pinned host memory (hipHostMalloc) is told apart from pageable memory like the runtime does it, by address range
 struct PinnedMap {
   std::mutex m;
@@ -195,7 +199,7 @@ struct PinnedMap {
 };
 inline PinnedMap& pinned() { static PinnedMap* p = new PinnedMap; return *p; }
 inline void* pinned_alloc(size_t n) {
-  void* p = malloc(n ? n : 1);
+  void* p = refuse_alloc() ? nullptr : malloc(n ? n : 1);
   if (p) { std::lock_guard<std::mutex> lk(pinned().m); pinned().range[(uintptr_t)p] = n ? n : 1; live_objects++; }
   return p;
 }
@@ -213,6 +217,7 @@ inline bool is_pinned(const void* q) {
 }
 
 inline void* device_alloc(size_t n) {
+  if (refuse_alloc()) return nullptr;
   void* p = malloc(n ? n : 1);
   if (p) live_objects++;
   static const bool poison = getenv("HOSTEMU_POISON") && atoi(getenv("HOSTEMU_POISON"));
@@ -288,3 +293,6 @@ inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
 
 // checker hook (tools/hostemu/check_group.py): the number of runtime objects alive
 extern "C" __attribute__((visibility("default"))) long long hostemu_live_objects(void) { return hostemu::live_objects.load(); }
+// checker hook (tools/hostemu/check_lifecycle.py): the nth next hipMalloc / hipHostMalloc of the process returns
+// hipErrorInvalidValue; 0 disarms
+extern "C" __attribute__((visibility("default"))) void hostemu_refuse_alloc(long long nth) { hostemu::refuse_countdown.store(nth); }

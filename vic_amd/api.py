@@ -166,8 +166,14 @@ class Model:
             raise VicGpuError("vicgpu_create failed with code %d (no GPU, or unsupported options)" % rc)
         self.h = h
         self._chk(self.lib.vicgpu_set_veglib(h, dom.veglib.shape[0], _d(np.ascontiguousarray(dom.veglib))))
-        self._chk(self.lib.vicgpu_set_domain(h, dom.ncell, dom.nhru, _d(dom.cell_params), _i(dom.hru_iparams),
+        self.set_domain(dom)
+
+    def set_domain(self, dom):
+        """vicgpu_set_domain: `dom` replaces the domain of this handle (its tables, state, outputs and forcing go with it;
+        the vegetation library stays).  Same options as the domain the handle was created for."""
+        self._chk(self.lib.vicgpu_set_domain(self.h, dom.ncell, dom.nhru, _d(dom.cell_params), _i(dom.hru_iparams),
                                              _d(dom.hru_dparams), _i(dom.cell_hru_offset), _i(dom.cell_hru_list)))
+        self.dom = dom
 
     def _chk(self, rc):
         if rc != 0:
@@ -436,8 +442,7 @@ class Group(Model):
             raise VicGpuError("vicgpu_group_create failed with code %d (no GPU, a device out of range, or unsupported options)" % rc)
         self.h = h
         self._chk(self.lib.vicgpu_set_veglib(h, dom.veglib.shape[0], _d(np.ascontiguousarray(dom.veglib))))
-        self._chk(self.lib.vicgpu_set_domain(h, dom.ncell, dom.nhru, _d(dom.cell_params), _i(dom.hru_iparams),
-                                             _d(dom.hru_dparams), _i(dom.cell_hru_offset), _i(dom.cell_hru_list)))
+        self.set_domain(dom)
 
     def shard_bounds(self):
         """[nshard+1]: shard k holds the cells [b[k], b[k+1])."""

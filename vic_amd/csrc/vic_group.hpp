@@ -367,15 +367,15 @@ int vicgpu_group_get_balance(vicgpu_group* g, double* pb) {
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) {
     vicgpu_ctx* c = g->ctx[k];
-    if (!c->put_on) return (int)VICGPU_ERR_STATE;
-    return d2h_cols(c, pb + g->c0(k), g->ncell, c->d_pb, sizeof(double), PB_NROW);
+    if (!c->dom.put_on) return (int)VICGPU_ERR_STATE;
+    return d2h_cols(c, pb + g->c0(k), g->ncell, c->dom.d_pb, sizeof(double), PB_NROW);
   });
 }
 
 int vicgpu_group_get_cell_errors(vicgpu_group* g, int* flags) {
   if (!g || !flags) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
-  return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->d_cell_err, sizeof(int), 1); });
+  return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->dom.d_cell_err, sizeof(int), 1); });
 }
 
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset) {

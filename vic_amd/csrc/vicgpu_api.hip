@@ -11,6 +11,7 @@
 //   vic_cell_reduce    one lane per cell: atmos->out_prec/out_rain/out_snow (full_energy.c:429-431) summed in hruList
 //                      order (deterministic, no atomics) and the Cv-weighted per-cell accumulators.
 //   vic_put_sum/_finish/_aggregate   put_data (put_data.c:7-760), the aggregated output variables (vic_putdata.hpp)
+// Host layer: every device buffer, pinned block, stream and event is held by a handle of vic_host.hpp.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -27,6 +29,7 @@
 #include "vic_glacier.hpp"
 #include "vic_profile.hpp"
 #include "vic_putdata.hpp"
+#include "vic_host.hpp"
 
 using namespace vic;
 
@@ -1360,21 +1363,42 @@ __global__ __launch_bounds__(256) void vic_state_records(const RArgs a) {
 constexpr int RB_LAG = 3, RB_DEPTH = RB_LAG + 1;
 struct FdChunk {
   int c0 = 0, ccount = 0;          // cells [c0, c0 + ccount)
-  int* d_glist = nullptr;          // their HRUs, ascending
+  DevBuf<int> d_glist;             // their HRUs, ascending
   int gcount = 0;
   LaunchMap map;                   // XCD-aware launch order when the chunk's list is regular (slot-major, every slot ccount cells)
-  int* d_list[2] = {nullptr, nullptr};   // work lists (HRU ids)
-  int *d_fb_list = nullptr, *d_fb_count = nullptr;   // IMPLICIT: HRUs whose Newton iteration failed this round
-  int* d_count = nullptr;          // counter block (CNT_*): segment sizes of the two lists, profile cursor, evaluation-only counts, pending total
-  int* d_elist[2] = {nullptr, nullptr};  // evaluation-only lists (flat, gcount entries): pending HRUs that need no solve
+  DevBuf<int> d_list[2];           // work lists (HRU ids)
+  DevBuf<int> d_fb_list, d_fb_count;   // IMPLICIT: HRUs whose Newton iteration failed this round
+  DevBuf<int> d_count;             // counter block (CNT_*): segment sizes of the two lists, profile cursor, evaluation-only counts, pending total
+  DevBuf<int> d_elist[2];          // evaluation-only lists (flat, gcount entries): pending HRUs that need no solve
   int list_cap = 0;                // entries per segment
-  int* h_count = nullptr;          // pinned read-back, RB_DEPTH slots of CNT_TOTAL
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;
-  hipEvent_t readback[RB_DEPTH] = {};
+  PinnedBuf<int> h_count;          // pinned read-back, RB_DEPTH slots of CNT_TOTAL
+  Stream stream;
+  Event done, readback[RB_DEPTH];
   std::string err;
   int status = 0;
   long long rounds = 0, steps = 0;
+};
+
+// Everything that lives exactly as long as a domain: vicgpu_set_domain builds it, free_domain drops it as a whole
+struct Domain {
+  int ncell = 0, nhru = 0;
+  bool domain_ready = false;       // set at the end of a successful vicgpu_set_domain
+  bool any_glacier = false;
+  DevBuf<double> d_cp, d_hpd, d_sd, d_flux, d_cell_out, d_accum;
+  DevBuf<int> d_hpi, d_si, d_cell_off, d_cell_list, d_hru_err, d_cell_err;
+  // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
+  bool fd = false;
+  DevBuf<unsigned long long> d_ctx;
+  DevBuf<double> d_pin, d_ts, d_pout;
+  DevBuf<int> d_hstate, d_pslot, d_hkey, d_lastexp, d_jl;
+  DevBuf<double> d_pimp;           // IMPLICIT only
+  std::vector<FdChunk> chunks;     // cell chunks, each an independent pipeline on its own stream
+  // put_data (vicgpu_out.h): output tables [nrow][ncell], allocated by vicgpu_put_data_config
+  bool put_on = false;
+  int out_nrow = 0;
+  OutLayout out_lay;
+  DevBuf<double> d_out_data, d_out_agg, d_pb;
+  DevBuf<unsigned char> d_rowagg;  // [out_nrow] aggregation type of every output row
 };
 
 struct vicgpu_ctx {
@@ -1382,81 +1406,45 @@ struct vicgpu_ctx {
   Opt o;
   int device;
   std::string err;
-  int ncell = 0, nhru = 0, nveg_rows = 0;
-  bool domain_ready = false;       // set at the end of a successful vicgpu_set_domain, cleared by free_domain
-  double *d_veglib = nullptr, *d_cp = nullptr, *d_hpd = nullptr, *d_sd = nullptr, *d_flux = nullptr, *d_forcing = nullptr,
-         *d_cell_out = nullptr, *d_accum = nullptr;
-  int *d_hpi = nullptr, *d_si = nullptr, *d_cell_off = nullptr, *d_cell_list = nullptr, *d_hru_err = nullptr, *d_cell_err = nullptr;
+  int nveg_rows = 0;
+  DevBuf<double> d_veglib;
+  Domain dom;
+  // forcing: d_forcing / d_snowflag / dmy / chunk_steps describe the CURRENT chunk = slot[cur] (views into the slot, which
+  // owns the memory and outlives a domain); the other slot takes the prefetch of the next one (vicgpu_prefetch_forcing*,
+  // vicgpu_swap_forcing)
+  double* d_forcing = nullptr;
   unsigned char* d_snowflag = nullptr;
-  // forcing: d_forcing / d_snowflag / dmy / chunk_steps describe the CURRENT chunk = slot[cur]; the other slot takes the
-  // prefetch of the next one (vicgpu_prefetch_forcing*, vicgpu_swap_forcing)
   std::vector<int> dmy;            // host copy [nsteps][VIC_NDMY]
   int chunk_steps = 0;
   struct ForcingSlot {
-    double *d_f = nullptr, *d_raw = nullptr;
-    unsigned char* d_s = nullptr;
-    size_t fcap = 0, scap = 0, rawcap = 0, stage_cap = 0;
-    void* h_stage = nullptr;       // pinned staging for pageable sources
+    DevBuf<double> d_f, d_raw;
+    DevBuf<unsigned char> d_s;
+    PinnedBuf<char> h_stage;       // pinned staging for pageable sources
     std::vector<int> dmy;
     int nsteps = 0;
-    hipEvent_t uploaded = nullptr; // copy stream: the chunk is in the slot
-    hipEvent_t released = nullptr; // context stream: every step that read the slot has been queued before it
+    Event uploaded;                // copy stream: the chunk is in the slot
+    Event released;                // context stream: every step that read the slot has been queued before it
     bool upload_pending = false, was_current = false;
   } slot[2];
   int cur = -1, staged = -1;
-  hipStream_t stream = nullptr, copy_stream = nullptr;
-  bool own_stream = true;
-  std::vector<hipEvent_t> ev;      // start/stop pairs of the last vicgpu_step call
+  Stream stream, copy_stream;      // `stream` may be borrowed (vicgpu_set_stream)
+  std::vector<Event> ev;           // start/stop pairs of the last vicgpu_step call
   int ev_used = 0;
   int write_fluxes = 1;
   int steps_done = 0;
-  bool any_glacier = false;
-  // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
-  bool fd = false;
-  unsigned long long* d_ctx = nullptr;
-  double *d_pin = nullptr, *d_ts = nullptr, *d_pout = nullptr;
-  int *d_hstate = nullptr, *d_pslot = nullptr, *d_hkey = nullptr, *d_lastexp = nullptr, *d_jl = nullptr;
-  double* d_pimp = nullptr;        // IMPLICIT only
   int profile_waves = 0;           // resident waves of the profile kernel
   int eval_list_pct = 30;          // sparse evaluation rounds (lane = pending HRU) once at most this percentage of the HRUs is pending
   bool node_newton = false;        // frozen-node root finder: safeguarded Newton instead of the reference's Brent iteration
-  std::vector<FdChunk> chunks;     // cell chunks, each an independent pipeline on its own stream
   int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
-  // put_data (vicgpu_out.h): output tables [nrow][ncell], allocated by vicgpu_put_data_config
-  bool put_on = false;
-  int out_step_ratio = 1, out_nrow = 0;
-  OutLayout out_lay;
-  double *d_out_data = nullptr, *d_out_agg = nullptr, *d_pb = nullptr;
-  unsigned char* d_rowagg = nullptr;   // [out_nrow] aggregation type of every output row
+  int out_step_ratio = 1;
 };
 
 static void free_domain(vicgpu_ctx* c) {
-  void* ps[] = {c->d_cp, c->d_hpd, c->d_sd, c->d_flux, c->d_cell_out, c->d_accum, c->d_hpi, c->d_si, c->d_cell_off, c->d_cell_list,
-                c->d_hru_err, c->d_cell_err, c->d_ctx, c->d_pin, c->d_ts, c->d_pout, c->d_hstate, c->d_pslot, c->d_hkey,
-                c->d_out_data, c->d_out_agg, c->d_pb, c->d_rowagg, c->d_pimp, c->d_lastexp, c->d_jl};
-  for (void* p : ps) HIPIGN(hipFree(p));
-  c->d_out_data = c->d_out_agg = c->d_pb = nullptr;
-  c->d_rowagg = nullptr;
-  c->d_pimp = nullptr; c->d_lastexp = nullptr; c->d_jl = nullptr;
-  c->put_on = false;
-  for (FdChunk& ch : c->chunks) {
-    HIPIGN(hipFree(ch.d_glist)); HIPIGN(hipFree(ch.d_list[0])); HIPIGN(hipFree(ch.d_list[1])); HIPIGN(hipFree(ch.d_count));
-    HIPIGN(hipFree(ch.d_elist[0])); HIPIGN(hipFree(ch.d_elist[1]));
-    HIPIGN(hipFree(ch.d_fb_list)); HIPIGN(hipFree(ch.d_fb_count));
-    if (ch.h_count) HIPIGN(hipHostFree(ch.h_count));
-    if (ch.done) HIPIGN(hipEventDestroy(ch.done));
-    for (hipEvent_t e : ch.readback) if (e) HIPIGN(hipEventDestroy(e));
-    if (ch.stream) HIPIGN(hipStreamDestroy(ch.stream));
-  }
-  c->chunks.clear();
-  c->domain_ready = false;
+  c->dom = Domain();
   c->chunk_steps = 0;              // a forcing chunk belongs to the domain it was pushed for (its rows are ncell wide)
   c->dmy.clear();
   c->cur = c->staged = -1;
   c->d_forcing = nullptr; c->d_snowflag = nullptr;
-  c->d_ctx = nullptr; c->d_pin = c->d_ts = c->d_pout = nullptr; c->d_hstate = c->d_pslot = c->d_hkey = nullptr;
-  c->d_cp = c->d_hpd = c->d_sd = c->d_flux = c->d_cell_out = c->d_accum = nullptr;
-  c->d_hpi = c->d_si = c->d_cell_off = c->d_cell_list = c->d_hru_err = c->d_cell_err = nullptr;
 }
 
 template <int NN>
@@ -1513,15 +1501,6 @@ static int profile_resident_waves(int device, bool newton) {
   return per_cu * ncu;
 }
 
-#define CHKCH(ch, call)                                                                               \
-  do {                                                                                                 \
-    hipError_t e_ = (call);                                                                            \
-    if (e_ != hipSuccess) {                                                                            \
-      (ch)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                   \
-      return VICGPU_ERR_HIP;                                                                           \
-    }                                                                                                  \
-  } while (0)
-
 // Counter block of a chunk.  Every group sits on its own 128-byte lines: the evaluation kernel's waves all read the pending
 // count while others append to the next list with atomics, and reads that share a line with those atomics queue behind them
 // in the L2 channel (measured: the dense evaluation rounds went from 0.6 to 1.4-2.5 ms when they did).
@@ -1534,8 +1513,8 @@ static inline int* cnt_evalonly(int* d_count, int l) { return d_count + CNT_EVAL
 // host thread: the number of Brent rounds is data dependent, so the pending count is read back once the first rounds
 // are through.
 static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* nevalonly) {
-  CHKCH(ch, hipMemcpyAsync(ch->h_count, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, ch->stream));
-  CHKCH(ch, hipStreamSynchronize(ch->stream));
+  HIPCHK(ch, hipMemcpyAsync(ch->h_count, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, ch->stream));
+  HIPCHK(ch, hipStreamSynchronize(ch->stream));
   int n = 0;
   for (int b = 0; b < NBUCKET; b++) n += ch->h_count[which * CNT_LIST_STRIDE + b];
   *nsolve = n;
@@ -1551,21 +1530,21 @@ static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* nevalonly) {
 static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
   const int Nn = c->o.Nnode;
   hipStream_t st = ch->stream;
-  if (c->any_glacier) CHKCH(ch, NODE_DISPATCH(Nn, launch_hru, ka, st, false, true));
-  CHKCH(ch, hipMemsetAsync(ch->d_count, 0, sizeof(int) * CNT_TOTAL, st));
+  if (c->dom.any_glacier) HIPCHK(ch, NODE_DISPATCH(Nn, launch_hru, ka, st, false, true));
+  HIPCHK(ch, hipMemsetAsync(ch->d_count, 0, sizeof(int) * CNT_TOTAL, st));
   int cur = 0;
   ka.phase = 0; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur); ka.list_cap = ch->list_cap;
-  CHKCH(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
+  HIPCHK(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
   PArgs pa;
-  pa.pin = c->d_pin; pa.ts = c->d_ts; pa.pout = c->d_pout; pa.pslot = c->d_pslot; pa.Nn = Nn; pa.NOFLUX = c->o.NOFLUX; pa.EXP_TRANS = c->o.EXP_TRANS;
-  pa.TFALLBACK = c->o.TFALLBACK; pa.next = ch->d_count + CNT_CURSOR; pa.cap = ch->list_cap; pa.jl = c->d_jl;
+  pa.pin = c->dom.d_pin; pa.ts = c->dom.d_ts; pa.pout = c->dom.d_pout; pa.pslot = c->dom.d_pslot; pa.Nn = Nn; pa.NOFLUX = c->o.NOFLUX; pa.EXP_TRANS = c->o.EXP_TRANS;
+  pa.TFALLBACK = c->o.TFALLBACK; pa.next = ch->d_count + CNT_CURSOR; pa.cap = ch->list_cap; pa.jl = c->dom.d_jl;
   EArgs ea;
-  ea.o = c->o; ea.ncell = c->ncell; ea.nhru = c->nhru; ea.Nn = Nn; ea.glist = ch->d_glist; ea.gcount = ch->gcount; ea.map = ch->map;
-  ea.cell_params = c->d_cp; ea.hpi = c->d_hpi; ea.ctx = c->d_ctx;
+  ea.o = c->o; ea.ncell = c->dom.ncell; ea.nhru = c->dom.nhru; ea.Nn = Nn; ea.glist = ch->d_glist; ea.gcount = ch->gcount; ea.map = ch->map;
+  ea.cell_params = c->dom.d_cp; ea.hpi = c->dom.d_hpi; ea.ctx = c->dom.d_ctx;
   ea.ctx_words = NODE_DISPATCH(Nn, ctx_words);
-  ea.pout = c->d_pout; ea.pslot = c->d_pslot; ea.ts = c->d_ts; ea.hstate = c->d_hstate; ea.profile_next = ch->d_count + CNT_CURSOR;
+  ea.pout = c->dom.d_pout; ea.pslot = c->dom.d_pslot; ea.ts = c->dom.d_ts; ea.hstate = c->dom.d_hstate; ea.profile_next = ch->d_count + CNT_CURSOR;
   ea.list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
-  ea.list_cap = ch->list_cap; ea.hkey = c->d_hkey; ea.implicit = c->o.IMPLICIT; ea.jl = c->d_jl;
+  ea.list_cap = ch->list_cap; ea.hkey = c->dom.d_hkey; ea.implicit = c->o.IMPLICIT; ea.jl = c->dom.d_jl;
   ea.veglib = c->d_veglib; ea.forcing = ka.forcing; ea.month = ka.dmy.month;
   const bool trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
   const int FREE_ROUNDS = 6;       // a Brent solve needs two bracket evaluations, a few iterations and the final evaluation
@@ -1582,10 +1561,10 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       if (c->o.IMPLICIT) {
         // the Newton iteration for every listed HRU; those it fails for go on the fall-back list, which the explicit kernel
         // (the same one, on that list) solves right after (func_surf_energy_bal.c:192-222)
-        CHKCH(ch, hipMemsetAsync(ch->d_fb_count, 0, sizeof(int) * (NBUCKET + 1), st));      // the fall-back segments and the work-list cursor
+        HIPCHK(ch, hipMemsetAsync(ch->d_fb_count, 0, sizeof(int) * (NBUCKET + 1), st));      // the fall-back segments and the work-list cursor
         IArgs ia;
-        ia.ncell = c->ncell; ia.nhru = c->nhru; ia.Nband = c->o.Nband; ia.pimp = c->d_pimp; ia.hpi = c->d_hpi; ia.cell_params = c->d_cp;
-        ia.hkey = c->d_hkey; ia.fb_list = ch->d_fb_list; ia.fb_count = ch->d_fb_count; ia.lastexp = c->d_lastexp; ia.cursor = ch->d_fb_count + NBUCKET;
+        ia.ncell = c->dom.ncell; ia.nhru = c->dom.nhru; ia.Nband = c->o.Nband; ia.pimp = c->dom.d_pimp; ia.hpi = c->dom.d_hpi; ia.cell_params = c->dom.d_cp;
+        ia.hkey = c->dom.d_hkey; ia.fb_list = ch->d_fb_list; ia.fb_count = ch->d_fb_count; ia.lastexp = c->dom.d_lastexp; ia.cursor = ch->d_fb_count + NBUCKET;
         {
           // persistent waves, a few per SIMD: a lane takes the next solve when its own ends (vic_implicit.hpp)
           int nblk = (nmax + 63) / 64;
@@ -1593,10 +1572,10 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
           if (nblk < 1) nblk = 1;
           hipLaunchKernelGGL(vic_profile_solve_implicit, dim3(nblk), dim3(64), 0, st, pa, ia);
         }
-        CHKCH(ch, hipGetLastError());
+        HIPCHK(ch, hipGetLastError());
         pa.list = ch->d_fb_list; pa.count = ch->d_fb_count;
       }
-      CHKCH(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
+      HIPCHK(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
       ea.list_next = ch->d_list[cur ^ 1]; ea.count_next = cnt_list(ch->d_count, cur ^ 1);
       ea.evalonly = cnt_evalonly(ch->d_count, cur ^ 1); ea.eo_list_next = ch->d_elist[cur ^ 1];
       ea.list_cur = ch->d_list[cur]; ea.count_cur = cnt_list(ch->d_count, cur);
@@ -1604,13 +1583,13 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       // the device switches to the lists by itself; once the host knows (RB_LAG rounds late) that it has, the grid shrinks too
       const bool sparse = npend >= 0 && npend <= ea.list_thr;
       hipLaunchKernelGGL(vic_surf_eval, dim3(sparse ? ((npend + 63) / 64 > 0 ? (npend + 63) / 64 : 1) : ea.map.nblocks(ch->gcount)), dim3(64), 0, st, ea);
-      CHKCH(ch, hipGetLastError());
+      HIPCHK(ch, hipGetLastError());
       cur ^= 1;
       ch->rounds++;
       if (trace_rounds) {       // tuning: what every round leaves pending (a host round trip per round)
         int n = 0, ne = 0;
         if (fd_read_count(ch, cur, &n, &ne) != VICGPU_OK) return VICGPU_ERR_HIP;
-        fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->chunks[0]), p, round, n, ne, ch->gcount);
+        fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->dom.chunks[0]), p, round, n, ne, ch->gcount);
       }
       // The list sizes of this round travel to the host behind the kernels just launched; the host looks at the copy issued
       // RB_LAG rounds ago, which has long arrived, so waiting for it never leaves the GPU idle.  The counts only shrink from
@@ -1618,13 +1597,13 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       if (round + 2 >= FREE_ROUNDS) {
         const int slot = round % RB_DEPTH;
         if (rb_first < 0) rb_first = round;
-        CHKCH(ch, hipMemcpyAsync(ch->h_count + slot * CNT_TOTAL, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, st));
-        CHKCH(ch, hipEventRecord(ch->readback[slot], st));
+        HIPCHK(ch, hipMemcpyAsync(ch->h_count + slot * CNT_TOTAL, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, st));
+        HIPCHK(ch, hipEventRecord(ch->readback[slot], st));
         rb_list[slot] = cur;
       }
       if (rb_first >= 0 && round - RB_LAG >= rb_first) {
         const int slot = (round - RB_LAG) % RB_DEPTH;
-        CHKCH(ch, hipEventSynchronize(ch->readback[slot]));
+        HIPCHK(ch, hipEventSynchronize(ch->readback[slot]));
         const int* h = ch->h_count + slot * CNT_TOTAL;
         int n = 0;
         for (int b = 0; b < NBUCKET; b++) n += h[rb_list[slot] * CNT_LIST_STRIDE + b];
@@ -1635,7 +1614,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       }
     }
     ka.phase = p; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur);
-    CHKCH(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
+    HIPCHK(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
     if (p < nsub) {
       int n = 0, ne = 0;
       const int r = fd_read_count(ch, cur, &n, &ne);
@@ -1650,20 +1629,20 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
 // put_data for cells [c0, c0 + ccount) after step s of the forcing chunk (s < 0: the initialisation call)
 static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, int ccount, int s) {
   OArgs a;
-  a.o = c->o; a.lay = c->out_lay; a.ncell = c->ncell; a.nhru = c->nhru; a.c0 = c0; a.ccount = ccount;
+  a.o = c->o; a.lay = c->dom.out_lay; a.ncell = c->dom.ncell; a.nhru = c->dom.nhru; a.c0 = c0; a.ccount = ccount;
   a.rec = s < 0 ? -1 : 0; a.out_step_ratio = c->out_step_ratio;
-  a.cell_off = c->d_cell_off; a.cell_list = c->d_cell_list; a.cell_params = c->d_cp; a.veglib = c->d_veglib;
-  a.hpi = c->d_hpi; a.hpd = c->d_hpd; a.sd = c->d_sd; a.si = c->d_si; a.flux = c->d_flux;
-  a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->ncell;
-  a.cell_out = c->d_cell_out; a.out_data = c->d_out_data; a.out_agg = c->d_out_agg; a.pb = c->d_pb;
+  a.cell_off = c->dom.d_cell_off; a.cell_list = c->dom.d_cell_list; a.cell_params = c->dom.d_cp; a.veglib = c->d_veglib;
+  a.hpi = c->dom.d_hpi; a.hpd = c->dom.d_hpd; a.sd = c->dom.d_sd; a.si = c->dom.d_si; a.flux = c->dom.d_flux;
+  a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->dom.ncell;
+  a.cell_out = c->dom.d_cell_out; a.out_data = c->dom.d_out_data; a.out_agg = c->dom.d_out_agg; a.pb = c->dom.d_pb;
   const unsigned nblk = (unsigned)((ccount + 63) / 64);
   // zero_output_list: the columns of these cells in every row
-  hipLaunchKernelGGL(vic_put_zero, dim3(nblk, (c->out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(vic_put_zero, dim3(nblk, (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
   if (c->o.Nnode > VIC_MID_NODES) hipLaunchKernelGGL(vic_put_sum_deep, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
   else hipLaunchKernelGGL(vic_put_sum, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
   hipLaunchKernelGGL(vic_put_finish, dim3(nblk), dim3(64), 0, st, a);
   if (s >= 0)
-    hipLaunchKernelGGL(vic_put_aggregate, dim3(nblk, (c->out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a, c->d_rowagg);
+    hipLaunchKernelGGL(vic_put_aggregate, dim3(nblk, (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a, c->dom.d_rowagg);
   return hipGetLastError();
 }
 
@@ -1677,8 +1656,8 @@ struct StepPlan {
 
 static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
   const size_t nsub = c->o.NR + 1;
-  ka.forcing = c->d_forcing + (size_t)s * VIC_NFORCE * nsub * c->ncell;
-  ka.snowflag = c->d_snowflag + (size_t)s * nsub * c->ncell;
+  ka.forcing = c->d_forcing + (size_t)s * VIC_NFORCE * nsub * c->dom.ncell;
+  ka.snowflag = c->d_snowflag + (size_t)s * nsub * c->dom.ncell;
   const int* d = &c->dmy[(size_t)s * VIC_NDMY];
   ka.dmy.month = d[VIC_DMY_MONTH]; ka.dmy.day_in_year = d[VIC_DMY_DAY_IN_YEAR]; ka.dmy.hour = d[VIC_DMY_HOUR];
   ka.dmy.day = d[VIC_DMY_DAY]; ka.dmy.year = d[VIC_DMY_YEAR];
@@ -1687,7 +1666,7 @@ static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
 // all steps of one vicgpu_step call for one chunk
 static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
   vicgpu_ctx* c = plan.c;
-  CHKCH(ch, hipSetDevice(c->device));
+  HIPCHK(ch, hipSetDevice(c->device));
   KArgs ka = plan.ka;
   CArgs ca = plan.ca;
   ka.glist = ch->d_glist; ka.gcount = ch->gcount; ka.map = ch->map;
@@ -1700,15 +1679,15 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
     const int r = fd_step(c, ch, ka);
     if (r != VICGPU_OK) return r;
     if (trace) {
-      CHKCH(ch, hipStreamSynchronize(ch->stream));
+      HIPCHK(ch, hipStreamSynchronize(ch->stream));
       fprintf(stderr, "[vicgpu] step %d hour %d: %.2f ms, %lld rounds\n", s, ka.dmy.hour,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), ch->rounds - r0);
     }
     hipLaunchKernelGGL(vic_cell_reduce, dim3((ch->ccount + 255) / 256), dim3(256), 0, ch->stream, ca);
-    CHKCH(ch, hipGetLastError());
-    if (c->put_on) CHKCH(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
+    HIPCHK(ch, hipGetLastError());
+    if (c->dom.put_on) HIPCHK(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
   }
-  CHKCH(ch, hipEventRecord(ch->done, ch->stream));
+  HIPCHK(ch, hipEventRecord(ch->done, ch->stream));
   return VICGPU_OK;
 }
 
@@ -1753,7 +1732,7 @@ int vicgpu_create(const vicgpu_options* opt, int device, vicgpu_ctx** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VICGPU_ERR_HIP;   // no CPU fallback: fail loudly
   if (device < 0 || device >= ndev) return VICGPU_ERR_ARG;
-  vicgpu_ctx* c = new vicgpu_ctx();
+  std::unique_ptr<vicgpu_ctx> c(new vicgpu_ctx());       // a failure below deletes it, and with it whatever it holds by then
   c->opt = *opt;
   c->device = device;
   Opt& o = c->o;
@@ -1768,17 +1747,11 @@ int vicgpu_create(const vicgpu_options* opt, int device, vicgpu_ctx** out) {
   // calc_surf_energy_bal.c:300-308: with QUICK_SOLVE and a surface energy balance the solver's EXP_TRANS is FALSE from the first
   // iteration to the final evaluation (the linear-spacing coefficients on the run's node geometry, whatever it is)
   if (o.QUICK_SOLVE && o.FULL_ENERGY) o.EXP_TRANS = 0;
-  if (hipSetDevice(device) != hipSuccess) { delete c; return VICGPU_ERR_HIP; }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess
-      || hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess
-      || hipEventCreateWithFlags(&c->slot[0].uploaded, hipEventDisableTiming) != hipSuccess
-      || hipEventCreateWithFlags(&c->slot[1].uploaded, hipEventDisableTiming) != hipSuccess
-      || hipEventCreateWithFlags(&c->slot[0].released, hipEventDisableTiming) != hipSuccess
-      || hipEventCreateWithFlags(&c->slot[1].released, hipEventDisableTiming) != hipSuccess) {
-    delete c;
-    return VICGPU_ERR_HIP;
-  }
-  *out = c;
+  HIPCHK(c, hipSetDevice(device));
+  HIPCHK(c, c->stream.create());
+  HIPCHK(c, c->copy_stream.create());
+  for (auto& sl : c->slot) { HIPCHK(c, sl.uploaded.create(hipEventDisableTiming)); HIPCHK(c, sl.released.create(hipEventDisableTiming)); }
+  *out = c.release();
   return VICGPU_OK;
 }
 
@@ -1786,50 +1759,22 @@ void vicgpu_destroy(vicgpu_ctx* c) {
   if (!c) return;
   HIPIGN(hipSetDevice(c->device));
   if (c->stream) HIPIGN(hipStreamSynchronize(c->stream));
-  if (getenv("VICGPU_STATS"))
-    for (size_t k = 0; k < c->chunks.size(); k++)
-      if (c->chunks[k].steps)
-        fprintf(stderr, "[vicgpu] chunk %zu: %d cells, %d HRUs, %lld steps, %.1f Brent rounds per step\n", k, c->chunks[k].ccount,
-                c->chunks[k].gcount, c->chunks[k].steps, (double)c->chunks[k].rounds / c->chunks[k].steps);
-  free_domain(c);
-  HIPIGN(hipFree(c->d_veglib));
   if (c->copy_stream) HIPIGN(hipStreamSynchronize(c->copy_stream));
-  for (auto& sl : c->slot) {
-    HIPIGN(hipFree(sl.d_f)); HIPIGN(hipFree(sl.d_s)); HIPIGN(hipFree(sl.d_raw));
-    if (sl.h_stage) HIPIGN(hipHostFree(sl.h_stage));
-    if (sl.uploaded) HIPIGN(hipEventDestroy(sl.uploaded));
-    if (sl.released) HIPIGN(hipEventDestroy(sl.released));
-  }
-  for (auto e : c->ev) HIPIGN(hipEventDestroy(e));
-  if (c->own_stream && c->stream) HIPIGN(hipStreamDestroy(c->stream));
-  if (c->copy_stream) HIPIGN(hipStreamDestroy(c->copy_stream));
-  delete c;
+  if (getenv("VICGPU_STATS"))
+    for (size_t k = 0; k < c->dom.chunks.size(); k++)
+      if (c->dom.chunks[k].steps)
+        fprintf(stderr, "[vicgpu] chunk %zu: %d cells, %d HRUs, %lld steps, %.1f Brent rounds per step\n", k, c->dom.chunks[k].ccount,
+                c->dom.chunks[k].gcount, c->dom.chunks[k].steps, (double)c->dom.chunks[k].rounds / c->dom.chunks[k].steps);
+  delete c;                        // the members release what they own (vic_host.hpp)
 }
 
 int vicgpu_set_veglib(vicgpu_ctx* c, int nrow, const double* veglib) {
   if (!c || !veglib || nrow != c->opt.nveg_types + 4) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPIGN(hipFree(c->d_veglib));
-  c->d_veglib = nullptr;
-  HIPCHK(c, hipMalloc(&c->d_veglib, sizeof(double) * nrow * VL_NFIELD));
+  HIPCHK(c, c->d_veglib.alloc((size_t)nrow * VL_NFIELD));
   HIPCHK(c, copy_on(c->stream, c->d_veglib, veglib, sizeof(double) * nrow * VL_NFIELD, hipMemcpyHostToDevice));
   c->nveg_rows = nrow;
   return VICGPU_OK;
-}
-
-static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cell_params, const int* hpi, const double* hpd,
-                           const int* cell_hru_offset, const int* cell_hru_list);
-
-int vicgpu_set_domain(vicgpu_ctx* c, int ncell, int nhru, const double* cell_params, const int* hpi, const double* hpd,
-                      const int* cell_hru_offset, const int* cell_hru_list) {
-  if (!c) return VICGPU_ERR_ARG;
-  const int r = set_domain_impl(c, ncell, nhru, cell_params, hpi, hpd, cell_hru_offset, cell_hru_list);
-  if (r == VICGPU_OK) c->domain_ready = true;
-  else if (r == VICGPU_ERR_HIP || r == VICGPU_ERR_NOMEM) {     // failed half-way: leave no partially built domain behind
-    HIPIGN(hipSetDevice(c->device));
-    free_domain(c);
-  }
-  return r;
 }
 
 static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cell_params, const int* hpi, const double* hpd,
@@ -1854,64 +1799,64 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
   }
   HIPCHK(c, hipSetDevice(c->device));
   free_domain(c);
-  c->ncell = ncell; c->nhru = nhru;
-  c->any_glacier = false;
-  for (int g = 0; g < nhru; g++) if (hpi[(size_t)HPI_IS_GLACIER * nhru + g]) c->any_glacier = true;
+  c->dom.ncell = ncell; c->dom.nhru = nhru;
+  c->dom.any_glacier = false;
+  for (int g = 0; g < nhru; g++) if (hpi[(size_t)HPI_IS_GLACIER * nhru + g]) c->dom.any_glacier = true;
   const size_t cp_n = (size_t)VICGPU_CP_NROW(c->opt.Nnode, c->opt.Nband) * ncell;
   const size_t cpx_n = (size_t)VIC_CPX_NROW(c->opt.Nnode, c->opt.Nband) * ncell;      // + the derived rows
   const size_t sd_n = (size_t)VICGPU_SD_NROW(c->opt.Nnode) * nhru, si_n = (size_t)VICGPU_SI_NROW(c->opt.Nnode) * nhru;
-  HIPCHK(c, hipMalloc(&c->d_cp, sizeof(double) * cpx_n));
-  HIPCHK(c, hipMalloc(&c->d_hpi, sizeof(int) * HPI_NROW * nhru));
-  HIPCHK(c, hipMalloc(&c->d_hpd, sizeof(double) * HPD_NROW * nhru));
-  HIPCHK(c, hipMalloc(&c->d_cell_off, sizeof(int) * (ncell + 1)));
-  HIPCHK(c, hipMalloc(&c->d_cell_list, sizeof(int) * nhru));
-  HIPCHK(c, hipMalloc(&c->d_sd, sizeof(double) * sd_n));
-  HIPCHK(c, hipMalloc(&c->d_si, sizeof(int) * si_n));
-  HIPCHK(c, hipMalloc(&c->d_flux, sizeof(double) * FX_NROW * nhru));
-  HIPCHK(c, hipMalloc(&c->d_cell_out, sizeof(double) * CO_NROW * ncell));
-  HIPCHK(c, hipMalloc(&c->d_accum, sizeof(double) * CA_NROW * ncell));
-  HIPCHK(c, hipMalloc(&c->d_hru_err, sizeof(int) * nhru));
-  HIPCHK(c, hipMalloc(&c->d_cell_err, sizeof(int) * ncell));
-  HIPCHK(c, copy_on(c->stream, c->d_cp, cell_params, sizeof(double) * cp_n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vic_derive_cell_params, dim3((ncell + 255) / 256), dim3(256), 0, c->stream, c->d_cp, ncell, c->opt.Nnode, c->opt.Nband);
+  HIPCHK(c, c->dom.d_cp.alloc(cpx_n));
+  HIPCHK(c, c->dom.d_hpi.alloc((size_t)HPI_NROW * nhru));
+  HIPCHK(c, c->dom.d_hpd.alloc((size_t)HPD_NROW * nhru));
+  HIPCHK(c, c->dom.d_cell_off.alloc((size_t)ncell + 1));
+  HIPCHK(c, c->dom.d_cell_list.alloc(nhru));
+  HIPCHK(c, c->dom.d_sd.alloc(sd_n));
+  HIPCHK(c, c->dom.d_si.alloc(si_n));
+  HIPCHK(c, c->dom.d_flux.alloc((size_t)FX_NROW * nhru));
+  HIPCHK(c, c->dom.d_cell_out.alloc((size_t)CO_NROW * ncell));
+  HIPCHK(c, c->dom.d_accum.alloc((size_t)CA_NROW * ncell));
+  HIPCHK(c, c->dom.d_hru_err.alloc(nhru));
+  HIPCHK(c, c->dom.d_cell_err.alloc(ncell));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_cp, cell_params, sizeof(double) * cp_n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(vic_derive_cell_params, dim3((ncell + 255) / 256), dim3(256), 0, c->stream, c->dom.d_cp, ncell, c->opt.Nnode, c->opt.Nband);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->d_hpi, hpi, sizeof(int) * HPI_NROW * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->d_hpd, hpd, sizeof(double) * HPD_NROW * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->d_cell_off, cell_hru_offset, sizeof(int) * (ncell + 1), hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->d_cell_list, cell_hru_list, sizeof(int) * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, fill_on(c->stream, c->d_sd, 0, sizeof(double) * sd_n));
-  HIPCHK(c, fill_on(c->stream, c->d_si, 0, sizeof(int) * si_n));
-  HIPCHK(c, fill_on(c->stream, c->d_flux, 0, sizeof(double) * FX_NROW * nhru));
-  HIPCHK(c, fill_on(c->stream, c->d_cell_out, 0, sizeof(double) * CO_NROW * ncell));
-  HIPCHK(c, fill_on(c->stream, c->d_accum, 0, sizeof(double) * CA_NROW * ncell));
-  HIPCHK(c, fill_on(c->stream, c->d_hru_err, 0, sizeof(int) * nhru));
-  HIPCHK(c, fill_on(c->stream, c->d_cell_err, 0, sizeof(int) * ncell));
-  c->fd = !c->o.QUICK_FLUX;
-  if (c->fd) {
+  HIPCHK(c, copy_on(c->stream, c->dom.d_hpi, hpi, sizeof(int) * HPI_NROW * nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_hpd, hpd, sizeof(double) * HPD_NROW * nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_cell_off, cell_hru_offset, sizeof(int) * (ncell + 1), hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_cell_list, cell_hru_list, sizeof(int) * nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_sd, 0, sizeof(double) * sd_n));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_si, 0, sizeof(int) * si_n));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_flux, 0, sizeof(double) * FX_NROW * nhru));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_cell_out, 0, sizeof(double) * CO_NROW * ncell));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_accum, 0, sizeof(double) * CA_NROW * ncell));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_hru_err, 0, sizeof(int) * nhru));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_cell_err, 0, sizeof(int) * ncell));
+  c->dom.fd = !c->o.QUICK_FLUX;
+  if (c->dom.fd) {
     const int Nn = c->o.Nnode;
     const size_t words = NODE_DISPATCH(Nn, ctx_words);
-    HIPCHK(c, hipMalloc(&c->d_ctx, sizeof(unsigned long long) * ctx_padded_words(words) * (((size_t)nhru + 63) / 64 * 64)));
-    HIPCHK(c, hipMalloc(&c->d_pin, sizeof(double) * (size_t)Nn * PREC * nhru));
-    HIPCHK(c, hipMalloc(&c->d_ts, sizeof(double) * nhru));
-    HIPCHK(c, hipMalloc(&c->d_pout, sizeof(double) * (size_t)pout_hru_stride(Nn) * nhru));
-    HIPCHK(c, hipMalloc(&c->d_pslot, sizeof(int) * nhru));
-    HIPCHK(c, hipMalloc(&c->d_hkey, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->d_hkey, 0, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->d_pslot, 0, sizeof(int) * nhru));
-    HIPCHK(c, hipMalloc(&c->d_hstate, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->d_hstate, 0, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->d_pin, 0, sizeof(double) * (size_t)Nn * PREC * nhru));
-    HIPCHK(c, fill_on(c->stream, c->d_pout, 0, sizeof(double) * (size_t)pout_hru_stride(Nn) * nhru));
+    HIPCHK(c, c->dom.d_ctx.alloc(ctx_padded_words(words) * (((size_t)nhru + 63) / 64 * 64)));
+    HIPCHK(c, c->dom.d_pin.alloc((size_t)Nn * PREC * nhru));
+    HIPCHK(c, c->dom.d_ts.alloc(nhru));
+    HIPCHK(c, c->dom.d_pout.alloc((size_t)pout_hru_stride(Nn) * nhru));
+    HIPCHK(c, c->dom.d_pslot.alloc(nhru));
+    HIPCHK(c, c->dom.d_hkey.alloc(nhru));
+    HIPCHK(c, fill_on(c->stream, c->dom.d_hkey, 0, sizeof(int) * nhru));
+    HIPCHK(c, fill_on(c->stream, c->dom.d_pslot, 0, sizeof(int) * nhru));
+    HIPCHK(c, c->dom.d_hstate.alloc(nhru));
+    HIPCHK(c, fill_on(c->stream, c->dom.d_hstate, 0, sizeof(int) * nhru));
+    HIPCHK(c, fill_on(c->stream, c->dom.d_pin, 0, sizeof(double) * (size_t)Nn * PREC * nhru));
+    HIPCHK(c, fill_on(c->stream, c->dom.d_pout, 0, sizeof(double) * (size_t)pout_hru_stride(Nn) * nhru));
     if (c->o.QUICK_SOLVE) {
-      HIPCHK(c, hipMalloc(&c->d_jl, sizeof(int) * nhru));
-      HIPCHK(c, fill_on(c->stream, c->d_jl, 0, sizeof(int) * nhru));
+      HIPCHK(c, c->dom.d_jl.alloc(nhru));
+      HIPCHK(c, fill_on(c->stream, c->dom.d_jl, 0, sizeof(int) * nhru));
     }
     if (c->o.IMPLICIT) {
-      HIPCHK(c, hipMalloc(&c->d_pimp, sizeof(double) * (size_t)Nn * PIMP * nhru));
-      HIPCHK(c, hipMalloc(&c->d_lastexp, sizeof(int) * nhru));
-      HIPCHK(c, fill_on(c->stream, c->d_pimp, 0, sizeof(double) * (size_t)Nn * PIMP * nhru));
-      HIPCHK(c, fill_on(c->stream, c->d_lastexp, 0xFF, sizeof(int) * nhru));
+      HIPCHK(c, c->dom.d_pimp.alloc((size_t)Nn * PIMP * nhru));
+      HIPCHK(c, c->dom.d_lastexp.alloc(nhru));
+      HIPCHK(c, fill_on(c->stream, c->dom.d_pimp, 0, sizeof(double) * (size_t)Nn * PIMP * nhru));
+      HIPCHK(c, fill_on(c->stream, c->dom.d_lastexp, 0xFF, sizeof(int) * nhru));
     }
     // frozen-node root finder (vic_profile.hpp): the option, overridable for A/B runs
     c->node_newton = c->opt.NODE_SOLVER == VIC_NODE_SOLVER_NEWTON;
@@ -1941,9 +1886,9 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
       if (pct >= 5 && pct <= 100) waves_pct = pct;
     }
     c->profile_waves = c->profile_waves * waves_pct / 100 > 0 ? c->profile_waves * waves_pct / 100 : 1;
-    c->chunks.resize(nchunk);
+    c->dom.chunks.resize(nchunk);
     for (int k = 0; k < nchunk; k++) {
-      FdChunk& ch = c->chunks[k];
+      FdChunk& ch = c->dom.chunks[k];
       ch.c0 = (int)((long long)ncell * k / nchunk);
       ch.ccount = (int)((long long)ncell * (k + 1) / nchunk) - ch.c0;
       std::vector<int> gl(cell_hru_list + cell_hru_offset[ch.c0], cell_hru_list + cell_hru_offset[ch.c0 + ch.ccount]);
@@ -1961,45 +1906,57 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
             }
         if (regular) { ch.map.nslot = nslot; ch.map.ccount = ch.ccount; }
       }
-      const size_t gb = sizeof(int) * (size_t)(ch.gcount > 0 ? ch.gcount : 1);
-      HIPCHK(c, hipMalloc(&ch.d_glist, gb));
+      const size_t gn = ch.gcount > 0 ? ch.gcount : 1;
+      HIPCHK(c, ch.d_glist.alloc(gn));
       ch.list_cap = ch.gcount > 0 ? ch.gcount : 1;
-      HIPCHK(c, hipMalloc(&ch.d_list[0], gb * NBUCKET));
-      HIPCHK(c, hipMalloc(&ch.d_list[1], gb * NBUCKET));
-      HIPCHK(c, hipMalloc(&ch.d_count, sizeof(int) * CNT_TOTAL));
-      HIPCHK(c, hipMalloc(&ch.d_elist[0], gb));
-      HIPCHK(c, hipMalloc(&ch.d_elist[1], gb));
+      HIPCHK(c, ch.d_list[0].alloc(gn * NBUCKET));
+      HIPCHK(c, ch.d_list[1].alloc(gn * NBUCKET));
+      HIPCHK(c, ch.d_count.alloc(CNT_TOTAL));
+      HIPCHK(c, ch.d_elist[0].alloc(gn));
+      HIPCHK(c, ch.d_elist[1].alloc(gn));
       if (c->o.IMPLICIT) {
-        HIPCHK(c, hipMalloc(&ch.d_fb_list, gb * NBUCKET));
-        HIPCHK(c, hipMalloc(&ch.d_fb_count, sizeof(int) * (NBUCKET + 1)));
+        HIPCHK(c, ch.d_fb_list.alloc(gn * NBUCKET));
+        HIPCHK(c, ch.d_fb_count.alloc(NBUCKET + 1));
       }
-      HIPCHK(c, hipHostMalloc(&ch.h_count, sizeof(int) * CNT_TOTAL * RB_DEPTH, hipHostMallocDefault));
+      HIPCHK(c, ch.h_count.alloc((size_t)CNT_TOTAL * RB_DEPTH));
       if (ch.gcount) HIPCHK(c, copy_on(c->stream, ch.d_glist, gl.data(), sizeof(int) * ch.gcount, hipMemcpyHostToDevice));
-      HIPCHK(c, hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking));
-      HIPCHK(c, hipEventCreateWithFlags(&ch.done, hipEventDisableTiming));
-      for (hipEvent_t& e : ch.readback) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      HIPCHK(c, ch.stream.create());
+      HIPCHK(c, ch.done.create(hipEventDisableTiming));
+      for (Event& e : ch.readback) HIPCHK(c, e.create(hipEventDisableTiming));
     }
   }
   return VICGPU_OK;
 }
 
+int vicgpu_set_domain(vicgpu_ctx* c, int ncell, int nhru, const double* cell_params, const int* hpi, const double* hpd,
+                      const int* cell_hru_offset, const int* cell_hru_list) {
+  if (!c) return VICGPU_ERR_ARG;
+  const int r = set_domain_impl(c, ncell, nhru, cell_params, hpi, hpd, cell_hru_offset, cell_hru_list);
+  if (r == VICGPU_OK) c->dom.domain_ready = true;
+  else if (r == VICGPU_ERR_HIP || r == VICGPU_ERR_NOMEM) {     // failed half-way: leave no partially built domain behind
+    HIPIGN(hipSetDevice(c->device));
+    free_domain(c);
+  }
+  return r;
+}
+
 int vicgpu_set_state(vicgpu_ctx* c, const double* sd, const int* si) {
   if (!c || !sd || !si) return VICGPU_ERR_ARG;
-  if (!c->domain_ready) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->d_sd, sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->d_si, si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_sd, sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_si, si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyHostToDevice));
   return VICGPU_OK;
 }
 
 int vicgpu_get_state(vicgpu_ctx* c, double* sd, int* si) {
   if (!c || !sd || !si) return VICGPU_ERR_ARG;
-  if (!c->domain_ready) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, sd, c->d_sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->nhru, hipMemcpyDeviceToHost));
-  HIPCHK(c, copy_on(c->stream, si, c->d_si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->nhru, hipMemcpyDeviceToHost));
+  HIPCHK(c, copy_on(c->stream, sd, c->dom.d_sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyDeviceToHost));
+  HIPCHK(c, copy_on(c->stream, si, c->dom.d_si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 
@@ -2077,7 +2034,7 @@ static bool is_pinned(const void* p) {
 static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, const void* src, size_t width, size_t rows,
                          size_t pitch, size_t stage_off) {
   if (!is_pinned(src)) {
-    char* st = (char*)sl.h_stage + stage_off;
+    char* st = sl.h_stage + stage_off;
     if (pitch == width) memcpy(st, src, width * rows);
     else for (size_t r = 0; r < rows; r++) memcpy(st + r * width, (const char*)src + r * pitch, width);
     return hipMemcpyAsync(dst, st, width * rows, hipMemcpyHostToDevice, c->copy_stream);
@@ -2086,54 +2043,49 @@ static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, 
   return hipMemcpy2DAsync(dst, width, src, pitch, width, rows, hipMemcpyHostToDevice, c->copy_stream);
 }
 
-// ld: cells per row of the source tables (c->ncell, or the global cell count when a group uploads one shard's columns)
+// ld: cells per row of the source tables (c->dom.ncell, or the global cell count when a group uploads one shard's columns)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
                          const int* dmy, double min_wind, int plapse, int ld) {
   if (!c || nsteps <= 0 || !dmy || (!raw && (!forcing || !snowflag))) return VICGPU_ERR_ARG;
-  if (!c->domain_ready) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   for (int s = 0; s < nsteps; s++) {
     int m = dmy[(size_t)s * VIC_NDMY + VIC_DMY_MONTH];
     if (m < 1 || m > 12) return VICGPU_ERR_ARG;          // month indexes the veg library tables
   }
   const size_t nsub = c->o.NR + 1;
-  const size_t fbytes = sizeof(double) * (size_t)nsteps * VIC_NFORCE * nsub * c->ncell;
-  const size_t sbytes = (size_t)nsteps * nsub * c->ncell;
-  const size_t rbytes = raw ? sizeof(double) * (size_t)nsteps * VIC_NRAW * c->o.dt * c->ncell : 0;
+  const size_t fbytes = sizeof(double) * (size_t)nsteps * VIC_NFORCE * nsub * c->dom.ncell;
+  const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell;
+  const size_t rbytes = raw ? sizeof(double) * (size_t)nsteps * VIC_NRAW * c->o.dt * c->dom.ncell : 0;
   const int t = (c->cur == 0) ? 1 : 0;
   vicgpu_ctx::ForcingSlot& sl = c->slot[t];
   // the slot's previous upload may still be reading its staging area; the steps that read the slot's device buffers were
   // queued before `released` was recorded (vicgpu_swap_forcing): the copy stream waits for that, not the host
   if (sl.upload_pending) { HIPCHK(c, hipEventSynchronize(sl.uploaded)); sl.upload_pending = false; }
   if (sl.was_current) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.released, 0));
-  const bool grow = fbytes > sl.fcap || sbytes > sl.scap || rbytes > sl.rawcap;
+  const bool grow = fbytes > sizeof(double) * sl.d_f.size() || sbytes > sl.d_s.size() || rbytes > sizeof(double) * sl.d_raw.size();
   if (grow) {                                            // re-allocation: nothing may still use the old buffers
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     if (sl.was_current) HIPCHK(c, hipEventSynchronize(sl.released));
-    if (fbytes > sl.fcap) { HIPIGN(hipFree(sl.d_f)); sl.d_f = nullptr; sl.fcap = 0; HIPCHK(c, hipMalloc(&sl.d_f, fbytes)); sl.fcap = fbytes; }
-    if (sbytes > sl.scap) { HIPIGN(hipFree(sl.d_s)); sl.d_s = nullptr; sl.scap = 0; HIPCHK(c, hipMalloc(&sl.d_s, sbytes)); sl.scap = sbytes; }
-    if (rbytes > sl.rawcap) { HIPIGN(hipFree(sl.d_raw)); sl.d_raw = nullptr; sl.rawcap = 0; HIPCHK(c, hipMalloc(&sl.d_raw, rbytes)); sl.rawcap = rbytes; }
+    HIPCHK(c, sl.d_f.reserve(fbytes / sizeof(double)));
+    HIPCHK(c, sl.d_s.reserve(sbytes));
+    HIPCHK(c, sl.d_raw.reserve(rbytes / sizeof(double)));
   }
   const size_t need_stage = raw ? (is_pinned(raw) ? 0 : rbytes) : ((is_pinned(forcing) ? 0 : fbytes) + (is_pinned(snowflag) ? 0 : sbytes));
-  if (need_stage > sl.stage_cap) {
-    if (sl.h_stage) HIPIGN(hipHostFree(sl.h_stage));
-    sl.h_stage = nullptr; sl.stage_cap = 0;
-    HIPCHK(c, hipHostMalloc(&sl.h_stage, need_stage, hipHostMallocDefault));
-    sl.stage_cap = need_stage;
-  }
+  HIPCHK(c, sl.h_stage.reserve(need_stage));
   if (raw) {
-    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * c->ncell, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * c->dom.ncell, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
     FArgs a;
-    a.nsteps = nsteps; a.ncell = c->ncell; a.dt = c->o.dt; a.snow_step = c->o.snow_step; a.NF = c->o.NF; a.NR = c->o.NR;
+    a.nsteps = nsteps; a.ncell = c->dom.ncell; a.dt = c->o.dt; a.snow_step = c->o.snow_step; a.NF = c->o.NF; a.NR = c->o.NR;
     a.temp_th_type = c->o.TEMP_TH_TYPE; a.Nband = c->o.Nband; a.Nnode = c->o.Nnode; a.plapse = plapse;
     a.min_wind = (double)(float)min_wind;        // options.MIN_WIND_SPEED is a float (vicNl_def.h:713)
-    a.raw = sl.d_raw; a.cell_params = c->d_cp; a.forcing = sl.d_f; a.snowflag = sl.d_s;
-    const size_t n = (size_t)nsteps * c->ncell;
+    a.raw = sl.d_raw; a.cell_params = c->dom.d_cp; a.forcing = sl.d_f; a.snowflag = sl.d_s;
+    const size_t n = (size_t)nsteps * c->dom.ncell;
     hipLaunchKernelGGL(vic_derive_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
     HIPCHK(c, hipGetLastError());
   } else {
-    HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * c->ncell, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
-    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->ncell, (size_t)nsteps * nsub, ld, is_pinned(forcing) ? 0 : fbytes));
+    HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * c->dom.ncell, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->dom.ncell, (size_t)nsteps * nsub, ld, is_pinned(forcing) ? 0 : fbytes));
   }
   HIPCHK(c, hipEventRecord(sl.uploaded, c->copy_stream));
   sl.upload_pending = true;
@@ -2145,11 +2097,11 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
 }
 
 int vicgpu_prefetch_forcing(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const int* dmy) {
-  return c ? prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1, c->ncell) : VICGPU_ERR_ARG;
+  return c ? prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1, c->dom.ncell) : VICGPU_ERR_ARG;
 }
 int vicgpu_prefetch_forcing_raw(vicgpu_ctx* c, int nsteps, const double* raw, const int* dmy, double min_wind_speed, int plapse) {
   if (!raw) return VICGPU_ERR_ARG;
-  return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->ncell) : VICGPU_ERR_ARG;
+  return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->dom.ncell) : VICGPU_ERR_ARG;
 }
 
 int vicgpu_swap_forcing(vicgpu_ctx* c) {
@@ -2180,56 +2132,55 @@ int vicgpu_get_forcing(vicgpu_ctx* c, int step, double* forcing, unsigned char* 
   HIPCHK(c, hipSetDevice(c->device));
   const size_t nsub = c->o.NR + 1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, forcing, c->d_forcing + (size_t)step * VIC_NFORCE * nsub * c->ncell, sizeof(double) * VIC_NFORCE * nsub * c->ncell, hipMemcpyDeviceToHost));
-  HIPCHK(c, copy_on(c->stream, snowflag, c->d_snowflag + (size_t)step * nsub * c->ncell, nsub * c->ncell, hipMemcpyDeviceToHost));
+  HIPCHK(c, copy_on(c->stream, forcing, c->d_forcing + (size_t)step * VIC_NFORCE * nsub * c->dom.ncell, sizeof(double) * VIC_NFORCE * nsub * c->dom.ncell, hipMemcpyDeviceToHost));
+  HIPCHK(c, copy_on(c->stream, snowflag, c->d_snowflag + (size_t)step * nsub * c->dom.ncell, nsub * c->dom.ncell, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 
 void* vicgpu_host_alloc(size_t bytes) {
-  void* p = nullptr;
-  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
-  return p;
+  PinnedBuf<char> b;               // the caller owns the block from here to vicgpu_host_free
+  return b.alloc(bytes ? bytes : 1) == hipSuccess ? b.release() : nullptr;
 }
-void vicgpu_host_free(void* p) { if (p) HIPIGN(hipHostFree(p)); }
+void vicgpu_host_free(void* p) { PinnedBuf<char> b((char*)p); }
 
 int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
   if (!c) return VICGPU_ERR_ARG;
-  if (!c->domain_ready || !c->d_veglib || !c->d_forcing || c->chunk_steps <= 0) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready || !c->d_veglib || !c->d_forcing || c->chunk_steps <= 0) return VICGPU_ERR_STATE;
   if (step0 < 0 || nsteps <= 0 || step0 + nsteps > c->chunk_steps) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   while ((int)c->ev.size() < 2 * nsteps) {
-    hipEvent_t e;
-    HIPCHK(c, hipEventCreate(&e));
-    c->ev.push_back(e);
+    Event e;
+    HIPCHK(c, e.create());
+    c->ev.push_back(std::move(e));
   }
   c->ev_used = 0;
   c->ev_steps = 0;
   StepPlan plan;
   plan.c = c; plan.step0 = step0; plan.nsteps = nsteps;
   KArgs& ka = plan.ka;
-  ka.o = c->o; ka.ncell = c->ncell; ka.nhru = c->nhru; ka.nveg_rows = c->nveg_rows;
-  ka.write_fluxes = (c->write_fluxes || c->put_on) ? 1 : 0;      // put_data reads every row of the flux table
-  ka.veglib = c->d_veglib; ka.cell_params = c->d_cp; ka.hpi = c->d_hpi; ka.hpd = c->d_hpd;
-  ka.sd = c->d_sd; ka.si = c->d_si; ka.flux = c->d_flux; ka.hru_err = c->d_hru_err;
-  ka.glist = nullptr; ka.gcount = c->nhru;
-  ka.ctx = c->d_ctx; ka.pin = c->d_pin; ka.ts = c->d_ts; ka.pout = c->d_pout; ka.pslot = c->d_pslot; ka.hstate = c->d_hstate; ka.hkey = c->d_hkey; ka.pimp = c->d_pimp; ka.lastexp = c->d_lastexp; ka.jl = c->d_jl; ka.list = nullptr; ka.count = nullptr; ka.list_cap = 0;
+  ka.o = c->o; ka.ncell = c->dom.ncell; ka.nhru = c->dom.nhru; ka.nveg_rows = c->nveg_rows;
+  ka.write_fluxes = (c->write_fluxes || c->dom.put_on) ? 1 : 0;      // put_data reads every row of the flux table
+  ka.veglib = c->d_veglib; ka.cell_params = c->dom.d_cp; ka.hpi = c->dom.d_hpi; ka.hpd = c->dom.d_hpd;
+  ka.sd = c->dom.d_sd; ka.si = c->dom.d_si; ka.flux = c->dom.d_flux; ka.hru_err = c->dom.d_hru_err;
+  ka.glist = nullptr; ka.gcount = c->dom.nhru;
+  ka.ctx = c->dom.d_ctx; ka.pin = c->dom.d_pin; ka.ts = c->dom.d_ts; ka.pout = c->dom.d_pout; ka.pslot = c->dom.d_pslot; ka.hstate = c->dom.d_hstate; ka.hkey = c->dom.d_hkey; ka.pimp = c->dom.d_pimp; ka.lastexp = c->dom.d_lastexp; ka.jl = c->dom.d_jl; ka.list = nullptr; ka.count = nullptr; ka.list_cap = 0;
   ka.phase = 0;
   CArgs& ca = plan.ca;
-  ca.ncell = c->ncell; ca.nhru = c->nhru; ca.c0 = 0; ca.ccount = c->ncell;
-  ca.cell_off = c->d_cell_off; ca.cell_list = c->d_cell_list; ca.hpd = c->d_hpd;
-  ca.hpi_glac = c->d_hpi + (size_t)HPI_IS_GLACIER * c->nhru;
-  ca.flux = c->d_flux; ca.sd = c->d_sd; ca.hru_err = c->d_hru_err; ca.cell_out = c->d_cell_out; ca.accum = c->d_accum;
-  ca.cell_err = c->d_cell_err;
-  if (!c->fd) {
+  ca.ncell = c->dom.ncell; ca.nhru = c->dom.nhru; ca.c0 = 0; ca.ccount = c->dom.ncell;
+  ca.cell_off = c->dom.d_cell_off; ca.cell_list = c->dom.d_cell_list; ca.hpd = c->dom.d_hpd;
+  ca.hpi_glac = c->dom.d_hpi + (size_t)HPI_IS_GLACIER * c->dom.nhru;
+  ca.flux = c->dom.d_flux; ca.sd = c->dom.d_sd; ca.hru_err = c->dom.d_hru_err; ca.cell_out = c->dom.d_cell_out; ca.accum = c->dom.d_accum;
+  ca.cell_err = c->dom.d_cell_err;
+  if (!c->dom.fd) {
     // QUICK_FLUX (implies Nnode == 3, vicgpu_create): one kernel per step, enqueued without blocking
     for (int s = step0; s < step0 + nsteps; s++) {
       set_step_inputs(c, ka, s);
       HIPCHK(c, hipEventRecord(c->ev[2 * (s - step0)], c->stream));
-      HIPCHK(c, launch_hru<3>(ka, c->stream, true, c->any_glacier));
+      HIPCHK(c, launch_hru<3>(ka, c->stream, true, c->dom.any_glacier));
       HIPCHK(c, hipEventRecord(c->ev[2 * (s - step0) + 1], c->stream));
-      hipLaunchKernelGGL(vic_cell_reduce, dim3((c->ncell + 255) / 256), dim3(256), 0, c->stream, ca);
+      hipLaunchKernelGGL(vic_cell_reduce, dim3((c->dom.ncell + 255) / 256), dim3(256), 0, c->stream, ca);
       HIPCHK(c, hipGetLastError());
-      if (c->put_on) HIPCHK(c, launch_put_data(c, c->stream, 0, c->ncell, s));
+      if (c->dom.put_on) HIPCHK(c, launch_put_data(c, c->stream, 0, c->dom.ncell, s));
       c->steps_done++;
     }
     c->ev_used = nsteps;
@@ -2239,26 +2190,26 @@ int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
   // finite-difference pipeline: every chunk runs all nsteps on its own stream (ordered after what is queued on the
   // context's stream, which in turn waits for every chunk before anything queued later)
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  for (FdChunk& ch : c->chunks) {
+  for (FdChunk& ch : c->dom.chunks) {
     HIPCHK(c, hipStreamWaitEvent(ch.stream, c->ev[0], 0));
     ch.status = VICGPU_OK;
     ch.err.clear();
   }
-  if (c->chunks.size() == 1) c->chunks[0].status = fd_chunk_run(plan, &c->chunks[0]);
+  if (c->dom.chunks.size() == 1) c->dom.chunks[0].status = fd_chunk_run(plan, &c->dom.chunks[0]);
   else {
     std::vector<std::thread> th;
-    for (FdChunk& ch : c->chunks) th.emplace_back([&plan, &ch]() { ch.status = fd_chunk_run(plan, &ch); });
+    for (FdChunk& ch : c->dom.chunks) th.emplace_back([&plan, &ch]() { ch.status = fd_chunk_run(plan, &ch); });
     for (std::thread& t : th) t.join();
   }
   int status = VICGPU_OK;
-  for (FdChunk& ch : c->chunks) {
+  for (FdChunk& ch : c->dom.chunks) {
     if (ch.status != VICGPU_OK && status == VICGPU_OK) { status = ch.status; c->err = ch.err; }
   }
   if (status != VICGPU_OK) {
-    for (FdChunk& ch : c->chunks) HIPIGN(hipStreamSynchronize(ch.stream));
+    for (FdChunk& ch : c->dom.chunks) HIPIGN(hipStreamSynchronize(ch.stream));
     return status;
   }
-  for (FdChunk& ch : c->chunks) HIPCHK(c, hipStreamWaitEvent(c->stream, ch.done, 0));
+  for (FdChunk& ch : c->dom.chunks) HIPCHK(c, hipStreamWaitEvent(c->stream, ch.done, 0));
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   c->ev_used = 1;
   c->ev_steps = nsteps;
@@ -2299,66 +2250,62 @@ static int d2h(vicgpu_ctx* c, void* dst, const void* src, size_t bytes) {
 // the same for a per-cell table [nrow][ncell] into the columns [0, ncell) of a host table whose rows are ld cells wide (a group
 // reads one shard's columns straight into the caller's global table)
 static int d2h_cols(vicgpu_ctx* c, void* dst, int ld, const void* src, size_t elem, int nrow) {
-  if (!c || !dst || !src || ld < c->ncell) return VICGPU_ERR_ARG;
-  if (ld == c->ncell) return d2h(c, dst, src, elem * nrow * c->ncell);
+  if (!c || !dst || !src || ld < c->dom.ncell) return VICGPU_ERR_ARG;
+  if (ld == c->dom.ncell) return d2h(c, dst, src, elem * nrow * c->dom.ncell);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(dst, elem * ld, src, elem * c->ncell, elem * c->ncell, nrow, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(dst, elem * ld, src, elem * c->dom.ncell, elem * c->dom.ncell, nrow, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VICGPU_OK;
 }
 
-int vicgpu_get_fluxes(vicgpu_ctx* c, double* flux) { return c ? d2h(c, flux, c->d_flux, sizeof(double) * FX_NROW * c->nhru) : VICGPU_ERR_ARG; }
-int vicgpu_get_cell_outputs(vicgpu_ctx* c, double* o) { return c ? d2h(c, o, c->d_cell_out, sizeof(double) * CO_NROW * c->ncell) : VICGPU_ERR_ARG; }
-int vicgpu_get_accum(vicgpu_ctx* c, double* a) { return c ? d2h(c, a, c->d_accum, sizeof(double) * CA_NROW * c->ncell) : VICGPU_ERR_ARG; }
-int vicgpu_get_cell_errors(vicgpu_ctx* c, int* f) { return c ? d2h(c, f, c->d_cell_err, sizeof(int) * c->ncell) : VICGPU_ERR_ARG; }
+int vicgpu_get_fluxes(vicgpu_ctx* c, double* flux) { return c ? d2h(c, flux, c->dom.d_flux, sizeof(double) * FX_NROW * c->dom.nhru) : VICGPU_ERR_ARG; }
+int vicgpu_get_cell_outputs(vicgpu_ctx* c, double* o) { return c ? d2h(c, o, c->dom.d_cell_out, sizeof(double) * CO_NROW * c->dom.ncell) : VICGPU_ERR_ARG; }
+int vicgpu_get_accum(vicgpu_ctx* c, double* a) { return c ? d2h(c, a, c->dom.d_accum, sizeof(double) * CA_NROW * c->dom.ncell) : VICGPU_ERR_ARG; }
+int vicgpu_get_cell_errors(vicgpu_ctx* c, int* f) { return c ? d2h(c, f, c->dom.d_cell_err, sizeof(int) * c->dom.ncell) : VICGPU_ERR_ARG; }
 
 int vicgpu_reset_accum(vicgpu_ctx* c) {
-  if (!c || !c->d_accum) return VICGPU_ERR_ARG;
+  if (!c || !c->dom.d_accum) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemsetAsync(c->d_accum, 0, sizeof(double) * CA_NROW * c->ncell, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_cell_err, 0, sizeof(int) * c->ncell, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->dom.d_accum, 0, sizeof(double) * CA_NROW * c->dom.ncell, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->dom.d_cell_err, 0, sizeof(int) * c->dom.ncell, c->stream));
   return VICGPU_OK;
 }
 
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld) {
-  if (!c || !c->d_cp || !eq || ld < c->ncell) return VICGPU_ERR_ARG;
+  if (!c || !c->dom.d_cp || !eq || ld < c->dom.ncell) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  double* d_eq = nullptr;
-  HIPCHK(c, hipMalloc(&d_eq, sizeof(double) * GMB_NROW * c->ncell));
+  DevBuf<double> d_eq;
+  HIPCHK(c, d_eq.alloc((size_t)GMB_NROW * c->dom.ncell));
   GArgs g;
-  g.o = c->o; g.ncell = c->ncell; g.nhru = c->nhru; g.reset = reset ? 1 : 0; g.cell_params = c->d_cp; g.cell_off = c->d_cell_off;
-  g.cell_list = c->d_cell_list; g.hpi = c->d_hpi; g.sd = c->d_sd; g.eq = d_eq;
-  hipLaunchKernelGGL(vic_glacier_fit, dim3((c->ncell + 63) / 64), dim3(64), 0, c->stream, g);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && ld == c->ncell) e = copy_on(c->stream, eq, d_eq, sizeof(double) * GMB_NROW * c->ncell, hipMemcpyDeviceToHost);
-  else if (e == hipSuccess) {
-    e = hipMemcpy2DAsync(eq, sizeof(double) * ld, d_eq, sizeof(double) * c->ncell, sizeof(double) * c->ncell, GMB_NROW,
-                         hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  g.o = c->o; g.ncell = c->dom.ncell; g.nhru = c->dom.nhru; g.reset = reset ? 1 : 0; g.cell_params = c->dom.d_cp; g.cell_off = c->dom.d_cell_off;
+  g.cell_list = c->dom.d_cell_list; g.hpi = c->dom.d_hpi; g.sd = c->dom.d_sd; g.eq = d_eq;
+  hipLaunchKernelGGL(vic_glacier_fit, dim3((c->dom.ncell + 63) / 64), dim3(64), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (ld == c->dom.ncell) HIPCHK(c, copy_on(c->stream, eq, d_eq, sizeof(double) * GMB_NROW * c->dom.ncell, hipMemcpyDeviceToHost));
+  else {
+    HIPCHK(c, hipMemcpy2DAsync(eq, sizeof(double) * ld, d_eq, sizeof(double) * c->dom.ncell, sizeof(double) * c->dom.ncell, GMB_NROW,
+                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  HIPIGN(hipFree(d_eq));
-  HIPCHK(c, e);
   return VICGPU_OK;
 }
-int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) { return c ? glacier_fit_impl(c, eq, reset, c->ncell) : VICGPU_ERR_ARG; }
+int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) { return c ? glacier_fit_impl(c, eq, reset, c->dom.ncell) : VICGPU_ERR_ARG; }
 
 int vicgpu_debug_pure(vicgpu_ctx* c, int fn, int n, const double* in, double* out) {
-  if (!c || !c->d_cp || fn < 0 || fn >= VICGPU_PURE_NFN_DEVICE || n <= 0 || !in || !out) return VICGPU_ERR_ARG;
+  if (!c || !c->dom.d_cp || fn < 0 || fn >= VICGPU_PURE_NFN_DEVICE || n <= 0 || !in || !out) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  double *d_in = nullptr, *d_out = nullptr;
-  HIPCHK(c, hipMalloc(&d_in, sizeof(double) * (size_t)n * VICGPU_PURE_NIN));
-  HIPCHK(c, hipMalloc(&d_out, sizeof(double) * (size_t)n));
+  DevBuf<double> d_in, d_out;
+  HIPCHK(c, d_in.alloc((size_t)n * VICGPU_PURE_NIN));
+  HIPCHK(c, d_out.alloc(n));
   HIPCHK(c, copy_on(c->stream, d_in, in, sizeof(double) * (size_t)n * VICGPU_PURE_NIN, hipMemcpyHostToDevice));
   DArgs d;
-  d.o = c->o; d.cell_params = c->d_cp; d.ncell = c->ncell; d.fn = fn; d.n = n; d.in = d_in; d.out = d_out;
+  d.o = c->o; d.cell_params = c->dom.d_cp; d.ncell = c->dom.ncell; d.fn = fn; d.n = n; d.in = d_in; d.out = d_out;
   hipLaunchKernelGGL(vic_debug_pure, dim3((n + 63) / 64), dim3(64), 0, c->stream, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
-  HIPIGN(hipFree(d_in)); HIPIGN(hipFree(d_out));
-  HIPCHK(c, e);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 
@@ -2370,39 +2317,35 @@ int vicgpu_debug_root_brent(vicgpu_ctx* c, int mode, int n, const double* bounds
   const int nv = off[n];
   if (nv > 0 && (!fvals || !xreq)) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  double *d_bounds = nullptr, *d_f = nullptr, *d_x = nullptr, *d_out = nullptr;
-  int* d_off = nullptr;
+  DevBuf<double> d_bounds, d_f, d_x, d_out;
+  DevBuf<int> d_off;
   const size_t nvs = nv > 0 ? (size_t)nv : 1;
-  hipError_t e = hipMalloc(&d_bounds, sizeof(double) * 2 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&d_off, sizeof(int) * ((size_t)n + 1));
-  if (e == hipSuccess) e = hipMalloc(&d_f, sizeof(double) * nvs);
-  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * nvs);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT);
-  if (e == hipSuccess) e = copy_on(c->stream, d_bounds, bounds, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = copy_on(c->stream, d_off, off, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice);
-  if (e == hipSuccess && nv > 0) e = copy_on(c->stream, d_f, fvals, sizeof(double) * (size_t)nv, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    RBArgs d;
-    d.n = n; d.bounds = d_bounds; d.off = d_off; d.fvals = d_f; d.xreq = d_x; d.out = d_out;
-    const dim3 grid((n + 63) / 64), block(64);
-    if (mode == VICGPU_BRENT_FULL) hipLaunchKernelGGL((vic_debug_root_brent<Brent>), grid, block, 0, c->stream, d);
-    else hipLaunchKernelGGL((vic_debug_root_brent<BrentLean>), grid, block, 0, c->stream, d);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && nv > 0) e = copy_on(c->stream, xreq, d_x, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT, hipMemcpyDeviceToHost);
-  HIPIGN(hipFree(d_bounds)); HIPIGN(hipFree(d_off)); HIPIGN(hipFree(d_f)); HIPIGN(hipFree(d_x)); HIPIGN(hipFree(d_out));
-  HIPCHK(c, e);
+  HIPCHK(c, d_bounds.alloc(2 * (size_t)n));
+  HIPCHK(c, d_off.alloc((size_t)n + 1));
+  HIPCHK(c, d_f.alloc(nvs));
+  HIPCHK(c, d_x.alloc(nvs));
+  HIPCHK(c, d_out.alloc((size_t)n * VICGPU_BRENT_NOUT));
+  HIPCHK(c, copy_on(c->stream, d_bounds, bounds, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, d_off, off, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
+  if (nv > 0) HIPCHK(c, copy_on(c->stream, d_f, fvals, sizeof(double) * (size_t)nv, hipMemcpyHostToDevice));
+  RBArgs d;
+  d.n = n; d.bounds = d_bounds; d.off = d_off; d.fvals = d_f; d.xreq = d_x; d.out = d_out;
+  const dim3 grid((n + 63) / 64), block(64);
+  if (mode == VICGPU_BRENT_FULL) hipLaunchKernelGGL((vic_debug_root_brent<Brent>), grid, block, 0, c->stream, d);
+  else hipLaunchKernelGGL((vic_debug_root_brent<BrentLean>), grid, block, 0, c->stream, d);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (nv > 0) HIPCHK(c, copy_on(c->stream, xreq, d_x, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost));
+  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 
 int vicgpu_debug_node_root(vicgpu_ctx* c, int mode, int n, const double* in, double* out) {
   if (!c || mode < 0 || mode > (VICGPU_NODE_NODE1 | VICGPU_NODE_NEWTON | VICGPU_NODE_EXP_TRANS) || n <= 0 || !in || !out) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  double *d_in = nullptr, *d_out = nullptr;
-  HIPCHK(c, hipMalloc(&d_in, sizeof(double) * (size_t)n * VICGPU_NODE_NIN));
-  HIPCHK(c, hipMalloc(&d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT));
+  DevBuf<double> d_in, d_out;
+  HIPCHK(c, d_in.alloc((size_t)n * VICGPU_NODE_NIN));
+  HIPCHK(c, d_out.alloc((size_t)n * VICGPU_NODE_NOUT));
   HIPCHK(c, copy_on(c->stream, d_in, in, sizeof(double) * (size_t)n * VICGPU_NODE_NIN, hipMemcpyHostToDevice));
   NRArgs d;
   d.n = n; d.EXP_TRANS = (mode & VICGPU_NODE_EXP_TRANS) != 0; d.in = d_in; d.out = d_out;
@@ -2413,11 +2356,9 @@ int vicgpu_debug_node_root(vicgpu_ctx* c, int mode, int n, const double* in, dou
     case VICGPU_NODE_NEWTON: hipLaunchKernelGGL((vic_debug_node_root<false, true>), grid, block, 0, c->stream, d); break;
     default: hipLaunchKernelGGL((vic_debug_node_root<true, true>), grid, block, 0, c->stream, d); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT, hipMemcpyDeviceToHost);
-  HIPIGN(hipFree(d_in)); HIPIGN(hipFree(d_out));
-  HIPCHK(c, e);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 
@@ -2425,14 +2366,8 @@ int vicgpu_set_stream(vicgpu_ctx* c, void* hip_stream) {
   if (!c) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (hip_stream) {
-    if (c->own_stream) HIPIGN(hipStreamDestroy(c->stream));
-    c->stream = (hipStream_t)hip_stream;
-    c->own_stream = false;
-  } else if (!c->own_stream) {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->own_stream = true;
-  }
+  if (hip_stream) c->stream.borrow((hipStream_t)hip_stream);
+  else if (c->stream.borrowed()) HIPCHK(c, c->stream.create());
   return VICGPU_OK;
 }
 
@@ -2445,58 +2380,50 @@ int vicgpu_set_write_fluxes(vicgpu_ctx* c, int on) {
 void* vicgpu_device_ptr(vicgpu_ctx* c, int which) {
   if (!c) return nullptr;
   switch (which) {
-    case VICGPU_PTR_STATE_D: return c->d_sd;
-    case VICGPU_PTR_STATE_I: return c->d_si;
-    case VICGPU_PTR_FLUX: return c->d_flux;
+    case VICGPU_PTR_STATE_D: return c->dom.d_sd;
+    case VICGPU_PTR_STATE_I: return c->dom.d_si;
+    case VICGPU_PTR_FLUX: return c->dom.d_flux;
     case VICGPU_PTR_FORCING: return c->d_forcing;
-    case VICGPU_PTR_ACCUM: return c->d_accum;
-    case VICGPU_PTR_CELL_OUT: return c->d_cell_out;
+    case VICGPU_PTR_ACCUM: return c->dom.d_accum;
+    case VICGPU_PTR_CELL_OUT: return c->dom.d_cell_out;
     default: return nullptr;
   }
 }
 
 static int state_records(vicgpu_ctx* c, double* host, bool gather) {
   if (!c || !host) return VICGPU_ERR_ARG;
-  if (!c->domain_ready) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t bytes = sizeof(double) * (size_t)VICGPU_SR_LEN(c->opt.Nnode) * c->nhru;
-  double* d_rec = nullptr;
-  int* d_mis = nullptr;
-  HIPCHK(c, hipMalloc(&d_rec, bytes));
-  hipError_t e = hipMalloc(&d_mis, sizeof(int));
-  int mismatch = 0;
-  if (e == hipSuccess) e = fill_on(c->stream, d_mis, 0, sizeof(int));
-  if (e == hipSuccess && !gather) e = copy_on(c->stream, d_rec, host, bytes, hipMemcpyHostToDevice);
+  const size_t nrec = (size_t)VICGPU_SR_LEN(c->opt.Nnode) * c->dom.nhru, bytes = sizeof(double) * nrec;
+  DevBuf<double> d_rec;
+  DevBuf<int> d_mis;
+  HIPCHK(c, d_rec.alloc(nrec));
+  HIPCHK(c, d_mis.alloc(1));
+  HIPCHK(c, fill_on(c->stream, d_mis, 0, sizeof(int)));
+  if (!gather) HIPCHK(c, copy_on(c->stream, d_rec, host, bytes, hipMemcpyHostToDevice));
   RArgs a;
-  a.nhru = c->nhru; a.Nn = c->opt.Nnode; a.cell_list = c->d_cell_list; a.hpi = c->d_hpi; a.sd = c->d_sd; a.si = c->d_si;
-  a.flux = c->d_flux; a.rec = d_rec; a.mismatch = d_mis;
-  if (e == hipSuccess && !gather) {
+  a.nhru = c->dom.nhru; a.Nn = c->opt.Nnode; a.cell_list = c->dom.d_cell_list; a.hpi = c->dom.d_hpi; a.sd = c->dom.d_sd; a.si = c->dom.d_si;
+  a.flux = c->dom.d_flux; a.rec = d_rec; a.mismatch = d_mis;
+  if (!gather) {
     // read side, pass 1: validate every record before anything is scattered (a reader that throws changes nothing)
-    std::vector<int> hpi_band(c->nhru), hpi_veg(c->nhru), list(c->nhru);
-    e = copy_on(c->stream, hpi_band.data(), c->d_hpi + (size_t)HPI_BAND * c->nhru, sizeof(int) * c->nhru, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_on(c->stream, hpi_veg.data(), c->d_hpi + (size_t)HPI_VEG_CLASS * c->nhru, sizeof(int) * c->nhru, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = copy_on(c->stream, list.data(), c->d_cell_list, sizeof(int) * c->nhru, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
-      const size_t L = VICGPU_SR_LEN(c->opt.Nnode);
-      for (int k = 0; k < c->nhru && !mismatch; k++)
-        if ((int)host[k * L + SR_BAND_INDEX] != hpi_band[list[k]] || (int)host[k * L + SR_VEG_CLASS] != hpi_veg[list[k]]) mismatch = k + 1;
-    }
+    std::vector<int> hpi_band(c->dom.nhru), hpi_veg(c->dom.nhru), list(c->dom.nhru);
+    HIPCHK(c, copy_on(c->stream, hpi_band.data(), c->dom.d_hpi + (size_t)HPI_BAND * c->dom.nhru, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_on(c->stream, hpi_veg.data(), c->dom.d_hpi + (size_t)HPI_VEG_CLASS * c->dom.nhru, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
+    HIPCHK(c, copy_on(c->stream, list.data(), c->dom.d_cell_list, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
+    const size_t L = VICGPU_SR_LEN(c->opt.Nnode);
+    for (int k = 0; k < c->dom.nhru; k++)
+      if ((int)host[k * L + SR_BAND_INDEX] != hpi_band[list[k]] || (int)host[k * L + SR_VEG_CLASS] != hpi_veg[list[k]]) {
+        c->err = "state record " + std::to_string(k) + ": band / vegetation class do not match the domain (write_model_state.c:179-188)";
+        return VICGPU_ERR_ARG;
+      }
   }
-  if (e == hipSuccess && !mismatch) {
-    const unsigned nblk = (unsigned)((c->nhru + 255) / 256);
-    if (gather) hipLaunchKernelGGL(vic_state_records<true>, dim3(nblk), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(vic_state_records<false>, dim3(nblk), dim3(256), 0, c->stream, a);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && gather) e = copy_on(c->stream, host, d_rec, bytes, hipMemcpyDeviceToHost);
-  }
-  HIPIGN(hipFree(d_rec)); HIPIGN(hipFree(d_mis));
-  HIPCHK(c, e);
-  if (mismatch) {
-    c->err = "state record " + std::to_string(mismatch - 1) + ": band / vegetation class do not match the domain (write_model_state.c:179-188)";
-    return VICGPU_ERR_ARG;
-  }
+  const unsigned nblk = (unsigned)((c->dom.nhru + 255) / 256);
+  if (gather) hipLaunchKernelGGL(vic_state_records<true>, dim3(nblk), dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL(vic_state_records<false>, dim3(nblk), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (gather) HIPCHK(c, copy_on(c->stream, host, d_rec, bytes, hipMemcpyDeviceToHost));
   return VICGPU_OK;
 }
 int vicgpu_get_state_records(vicgpu_ctx* c, double* rec) { return state_records(c, rec, true); }
@@ -2520,46 +2447,50 @@ int vicgpu_out_var_nelem(const vicgpu_options* opt, int id) {
 
 int vicgpu_put_data_config(vicgpu_ctx* c, int out_step_ratio) {
   if (!c || out_step_ratio < 1) return VICGPU_ERR_ARG;
-  if (!c->domain_ready || !c->d_veglib) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready || !c->d_veglib) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // the tree-line adjustment factor of every band (a function of the domain and the vegetation library's overstory flags)
-  hipLaunchKernelGGL(vic_derive_tree_adjust, dim3((c->ncell + 63) / 64), dim3(64), 0, c->stream, c->d_cp, c->ncell, c->nhru, c->opt.Nnode,
-                     c->opt.Nband, c->d_cell_off, c->d_cell_list, c->d_hpi, c->d_hpd, c->d_veglib);
+  hipLaunchKernelGGL(vic_derive_tree_adjust, dim3((c->dom.ncell + 63) / 64), dim3(64), 0, c->stream, c->dom.d_cp, c->dom.ncell, c->dom.nhru, c->opt.Nnode,
+                     c->opt.Nband, c->dom.d_cell_off, c->dom.d_cell_list, c->dom.d_hpi, c->dom.d_hpd, c->d_veglib);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   int r = 0;
   for (int v = 0; v < VOUT_NVAR; v++) {
-    c->out_lay.off[v] = r; c->out_lay.agg[v] = vout_agg_host[v];
+    c->dom.out_lay.off[v] = r; c->dom.out_lay.agg[v] = vout_agg_host[v];
     r += vout_kind_nelem(vout_kind_host[v], c->opt.Nnode, c->opt.Nband, c->opt.FROZEN_SOIL);
   }
-  c->out_lay.off[VOUT_NVAR] = r;
-  c->out_nrow = r;
+  c->dom.out_lay.off[VOUT_NVAR] = r;
+  c->dom.out_nrow = r;
   c->out_step_ratio = out_step_ratio;
   std::vector<unsigned char> rowagg(r);
   for (int v = 0; v < VOUT_NVAR; v++) {
     const bool by_finish = (v == VOUT_AERO_RESIST || v == VOUT_AERO_RESIST1 || v == VOUT_AERO_RESIST2);   // vic_put_finish
-    for (int k = c->out_lay.off[v]; k < c->out_lay.off[v + 1]; k++) rowagg[k] = (unsigned char)(by_finish ? VOUT_AGG_SKIP : vout_agg_host[v]);
+    for (int k = c->dom.out_lay.off[v]; k < c->dom.out_lay.off[v + 1]; k++) rowagg[k] = (unsigned char)(by_finish ? VOUT_AGG_SKIP : vout_agg_host[v]);
   }
-  if (!c->d_out_data) {
-    HIPCHK(c, hipMalloc(&c->d_out_data, sizeof(double) * (size_t)r * c->ncell));
-    HIPCHK(c, hipMalloc(&c->d_out_agg, sizeof(double) * (size_t)r * c->ncell));
-    HIPCHK(c, hipMalloc(&c->d_pb, sizeof(double) * (size_t)PBX_NROW * c->ncell));
-    HIPCHK(c, hipMalloc(&c->d_rowagg, (size_t)r));
+  c->dom.put_on = false;
+  if (!c->dom.d_out_data) {        // all four tables or none: a failed call leaves nothing half-present for the next one
+    DevBuf<double> out_data, out_agg, pb;
+    DevBuf<unsigned char> d_rowagg;
+    HIPCHK(c, out_data.alloc((size_t)r * c->dom.ncell));
+    HIPCHK(c, out_agg.alloc((size_t)r * c->dom.ncell));
+    HIPCHK(c, pb.alloc((size_t)PBX_NROW * c->dom.ncell));
+    HIPCHK(c, d_rowagg.alloc(r));
+    c->dom.d_out_data = std::move(out_data); c->dom.d_out_agg = std::move(out_agg); c->dom.d_pb = std::move(pb); c->dom.d_rowagg = std::move(d_rowagg);
   }
-  HIPCHK(c, copy_on(c->stream, c->d_rowagg, rowagg.data(), (size_t)r, hipMemcpyHostToDevice));
-  HIPCHK(c, fill_on(c->stream, c->d_out_data, 0, sizeof(double) * (size_t)r * c->ncell));
-  HIPCHK(c, fill_on(c->stream, c->d_out_agg, 0, sizeof(double) * (size_t)r * c->ncell));
-  HIPCHK(c, fill_on(c->stream, c->d_pb, 0, sizeof(double) * (size_t)PBX_NROW * c->ncell));
-  c->put_on = true;
+  HIPCHK(c, copy_on(c->stream, c->dom.d_rowagg, rowagg.data(), (size_t)r, hipMemcpyHostToDevice));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_out_data, 0, sizeof(double) * (size_t)r * c->dom.ncell));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_out_agg, 0, sizeof(double) * (size_t)r * c->dom.ncell));
+  HIPCHK(c, fill_on(c->stream, c->dom.d_pb, 0, sizeof(double) * (size_t)PBX_NROW * c->dom.ncell));
+  c->dom.put_on = true;
   return VICGPU_OK;
 }
 
 int vicgpu_put_data_init(vicgpu_ctx* c) {
   if (!c) return VICGPU_ERR_ARG;
-  if (!c->domain_ready || !c->put_on || !c->d_veglib) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready || !c->dom.put_on || !c->d_veglib) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, launch_put_data(c, c->stream, 0, c->ncell, -1));
+  HIPCHK(c, launch_put_data(c, c->stream, 0, c->dom.ncell, -1));
   return VICGPU_OK;
 }
 
@@ -2576,73 +2507,72 @@ static int out_rows(const vicgpu_ctx* c, int nvar, const int* ids, std::vector<i
   rows.clear();
   for (int k = 0; k < nvar; k++) {
     if (ids[k] < 0 || ids[k] >= VOUT_NVAR) return -1;
-    for (int r = c->out_lay.off[ids[k]]; r < c->out_lay.off[ids[k] + 1]; r++) rows.push_back(r);
+    for (int r = c->dom.out_lay.off[ids[k]]; r < c->dom.out_lay.off[ids[k] + 1]; r++) rows.push_back(r);
   }
   return (int)rows.size();
 }
 
-// ld: cells per row of `out` (c->ncell, or the global cell count when a group writes one shard's columns)
+// ld: cells per row of `out` (c->dom.ncell, or the global cell count when a group writes one shard's columns)
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld) {
-  if (!c || nvar < 0 || (nvar > 0 && (!var_ids || !out)) || ld < c->ncell) return VICGPU_ERR_ARG;
-  if (!c->put_on) return VICGPU_ERR_STATE;
+  if (!c || nvar < 0 || (nvar > 0 && (!var_ids || !out)) || ld < c->dom.ncell) return VICGPU_ERR_ARG;
+  if (!c->dom.put_on) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<int> rows;
   const int nr = out_rows(c, nvar, var_ids, rows);
   if (nr < 0) return VICGPU_ERR_ARG;
   if (nr > 0) {
-    int* d_rows = nullptr;
-    float* d_f = nullptr;
-    const size_t n = (size_t)nr * c->ncell;
-    HIPCHK(c, hipMalloc(&d_rows, sizeof(int) * nr));
-    hipError_t e = hipMalloc(&d_f, sizeof(float) * n);
-    if (e == hipSuccess) e = copy_on(c->stream, d_rows, rows.data(), sizeof(int) * nr, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(vic_out_rows_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_out_agg, d_rows, nr, c->ncell, d_f);
-      e = hipGetLastError();
+    DevBuf<int> d_rows;
+    DevBuf<float> d_f;
+    const size_t n = (size_t)nr * c->dom.ncell;
+    HIPCHK(c, d_rows.alloc(nr));
+    HIPCHK(c, d_f.alloc(n));
+    HIPCHK(c, copy_on(c->stream, d_rows, rows.data(), sizeof(int) * nr, hipMemcpyHostToDevice));
+    const int* rows_arg = d_rows;
+    float* f_arg = d_f;
+    hipLaunchKernelGGL(vic_out_rows_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->dom.d_out_agg, rows_arg, nr,
+                       c->dom.ncell, f_arg);
+    HIPCHK(c, hipGetLastError());
+    if (ld == c->dom.ncell) HIPCHK(c, copy_on(c->stream, out, d_f, sizeof(float) * n, hipMemcpyDeviceToHost));
+    else {
+      HIPCHK(c, hipMemcpy2DAsync(out, sizeof(float) * ld, d_f, sizeof(float) * c->dom.ncell, sizeof(float) * c->dom.ncell, nr,
+                                 hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    if (e == hipSuccess && ld == c->ncell) e = copy_on(c->stream, out, d_f, sizeof(float) * n, hipMemcpyDeviceToHost);
-    else if (e == hipSuccess) {
-      e = hipMemcpy2DAsync(out, sizeof(float) * ld, d_f, sizeof(float) * c->ncell, sizeof(float) * c->ncell, nr, hipMemcpyDeviceToHost,
-                           c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    HIPIGN(hipFree(d_rows)); HIPIGN(hipFree(d_f));
-    HIPCHK(c, e);
   }
-  if (reset) HIPCHK(c, fill_on(c->stream, c->d_out_agg, 0, sizeof(double) * (size_t)c->out_nrow * c->ncell));   // vicNl.c:599-606
+  if (reset) HIPCHK(c, fill_on(c->stream, c->dom.d_out_agg, 0, sizeof(double) * (size_t)c->dom.out_nrow * c->dom.ncell));   // vicNl.c:599-606
   return VICGPU_OK;
 }
 int vicgpu_get_outputs(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset) {
-  return c ? get_outputs_impl(c, nvar, var_ids, out, reset, c->ncell) : VICGPU_ERR_ARG;
+  return c ? get_outputs_impl(c, nvar, var_ids, out, reset, c->dom.ncell) : VICGPU_ERR_ARG;
 }
 
 int vicgpu_get_output_data(vicgpu_ctx* c, int nvar, const int* var_ids, int which, double* out) {
   if (!c || nvar <= 0 || !var_ids || !out || which < 0 || which > 1) return VICGPU_ERR_ARG;
-  if (!c->put_on) return VICGPU_ERR_STATE;
+  if (!c->dom.put_on) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   size_t at = 0;
   for (int k = 0; k < nvar; k++) {
     if (var_ids[k] < 0 || var_ids[k] >= VOUT_NVAR) return VICGPU_ERR_ARG;
-    const int r0 = c->out_lay.off[var_ids[k]], ne = c->out_lay.off[var_ids[k] + 1] - r0;
-    HIPCHK(c, copy_on(c->stream, out + at, (which ? c->d_out_agg : c->d_out_data) + (size_t)r0 * c->ncell, sizeof(double) * (size_t)ne * c->ncell, hipMemcpyDeviceToHost));
-    at += (size_t)ne * c->ncell;
+    const int r0 = c->dom.out_lay.off[var_ids[k]], ne = c->dom.out_lay.off[var_ids[k] + 1] - r0;
+    HIPCHK(c, copy_on(c->stream, out + at, (which ? c->dom.d_out_agg : c->dom.d_out_data) + (size_t)r0 * c->dom.ncell, sizeof(double) * (size_t)ne * c->dom.ncell, hipMemcpyDeviceToHost));
+    at += (size_t)ne * c->dom.ncell;
   }
   return VICGPU_OK;
 }
 
 int vicgpu_get_balance(vicgpu_ctx* c, double* pb) {
   if (!c || !pb) return VICGPU_ERR_ARG;
-  if (!c->put_on) return VICGPU_ERR_STATE;
-  return d2h(c, pb, c->d_pb, sizeof(double) * (size_t)PB_NROW * c->ncell);
+  if (!c->dom.put_on) return VICGPU_ERR_STATE;
+  return d2h(c, pb, c->dom.d_pb, sizeof(double) * (size_t)PB_NROW * c->dom.ncell);
 }
 
 int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
   if (!c || !flux) return VICGPU_ERR_ARG;
-  if (!c->domain_ready) return VICGPU_ERR_STATE;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->d_flux, flux, sizeof(double) * FX_NROW * c->nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, copy_on(c->stream, c->dom.d_flux, flux, sizeof(double) * FX_NROW * c->dom.nhru, hipMemcpyHostToDevice));
   return VICGPU_OK;
 }
 
