@@ -40,6 +40,11 @@ namespace vic {
 // (more than VIC_MID_NODES nodes) shares these segments: its frozen-node counts of 25 and more take the top one of each half.
 constexpr int NBUCKET = 2 * (VIC_MID_NODES + 2);
 static_assert(NBUCKET <= 64, "one lane per work-list segment when the pending total is summed");
+// Next to the keyed work list the evaluation kernel keeps a flat list of every HRU a round leaves pending (solve or not), which
+// its sparse rounds are formed from.  Every wave appends its pending lanes as one chunk in lane order to stripe
+// blockIdx.x % PEND_STRIPES: 64 consecutive entries of a stripe come from a few producing waves, i.e. a few context slabs.
+// Each stripe's fill counter sits on its own 128-byte line (PEND_CNT_STRIDE ints apart).
+constexpr int PEND_STRIPES = 64, PEND_CNT_STRIDE = 32;
 
 struct PArgs {
   const double* __restrict__ pin;    // item blocks [nhru][Nn][PREC]
@@ -51,11 +56,14 @@ struct PArgs {
   int cap;
   int* next;                         // work-list cursor (zero at launch; the evaluation kernel clears it again)
   int* count_zero;                   // segment counters [NBUCKET] of the list the following evaluation kernel appends to (cleared here)
-  int* evalonly_zero;                // counter of HRUs whose next evaluation needs no solve (cleared here)
-  // the number of evaluations pending after this kernel = entries of the round's work list + evaluation-only HRUs of the round
-  // before, summed here (block 0) into ONE word on its own cache line for the waves of the evaluation kernel
+  // the number of evaluations pending after this kernel = entries of the flat pending list the evaluation kernel of the round
+  // before has left (after the opening stage, which fills the keyed list only: entries of that), summed here (block 0) into
+  // ONE word on its own cache line for the waves of the evaluation kernel; the stripe fills are packed into a dense prefix
+  // array next to it, so that those waves never read the lines their producers append to
   const int* pend_counts;            // [NBUCKET] (the round's list; not `count` when this launch works on IMPLICIT's fall-back list)
-  const int* pend_eo;
+  const int* pend_stripes;           // fill counters of the round's flat list [PEND_STRIPES], PEND_CNT_STRIDE apart
+  int* pend_stripes_zero;            // ... and of the one the following evaluation kernel appends to (cleared here)
+  int* pend_prefix;                  // [PEND_STRIPES + 1] entries before each stripe of the round's flat list
   int* pend_out;
   int Nn, NOFLUX, EXP_TRANS, TFALLBACK;
   const int* jl;                     // QUICK_SOLVE: [nhru] nodes 1 .. jl - 1 are solved (calc_surf_energy_bal.c:289-299), or null: all
@@ -306,6 +314,24 @@ VIC_DEV int profile_pick(const PArgs& a, const int* bcount, int slot) {
   return a.list[found];
 }
 
+// Block 0's share of the pending-list housekeeping between two evaluation launches (one wave): clears the stripe counters of
+// the next flat list, packs those of the current one into the prefix array and publishes the pending total.
+static_assert(PEND_STRIPES == 64, "one lane per stripe");
+VIC_DEV void pend_pack(const PArgs& a, int lane, int keyed_total) {
+  a.pend_stripes_zero[lane * PEND_CNT_STRIDE] = 0;
+  const int cnt = a.pend_stripes[lane * PEND_CNT_STRIDE];
+  int incl = cnt;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl(incl, lane >= off ? lane - off : lane);
+    if (lane >= off) incl += up;
+  }
+  a.pend_prefix[lane + 1] = incl;
+  if (lane == 0) a.pend_prefix[0] = 0;
+  const int total = __shfl(incl, 63);
+  if (lane == 0) *a.pend_out = total > 0 ? total : keyed_total;
+}
+
 // ------------------------------------------------------------------------------------------------
 // 10 nodes (the sample global file's and BASELINE's node count): node constants and temperatures in registers
 // ------------------------------------------------------------------------------------------------
@@ -321,11 +347,10 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
   for (int b = lane; b < NBUCKET; b += 64) bcount[b] = a.count[b];
   if (blockIdx.x == 0) {
     for (int b = lane; b < NBUCKET; b += 64) a.count_zero[b] = 0;
-    if (lane == 0) *a.evalonly_zero = 0;
     int v = (lane < NBUCKET) ? a.pend_counts[lane] : 0;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl(v, lane ^ off);
-    if (lane == 0) *a.pend_out = v + *a.pend_eo;
+    pend_pack(a, lane, v);
   }
   __syncthreads();
   int n = 0;
@@ -484,11 +509,10 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
   for (int b = lane; b < NBUCKET; b += 64) bcount[b] = a.count[b];
   if (blockIdx.x == 0) {
     for (int b = lane; b < NBUCKET; b += 64) a.count_zero[b] = 0;
-    if (lane == 0) *a.evalonly_zero = 0;
     int v = (lane < NBUCKET) ? a.pend_counts[lane] : 0;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl(v, lane ^ off);
-    if (lane == 0) *a.pend_out = v + *a.pend_eo;
+    pend_pack(a, lane, v);
   }
   __syncthreads();
   int n = 0;

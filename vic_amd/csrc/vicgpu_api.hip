@@ -122,7 +122,7 @@ struct KArgs {
 // (a handful of pages) instead of one row per word spread over the whole table, and inside the slab every lane owns runs of
 // G consecutive words: [hru / 64][word / G][hru % 64][G].  G = 1 is the plain [word][lane] tiling (8-byte-per-lane rows run
 // the load path at half its rate); G = 2 makes every access 16 bytes; G = 8 gives a lane whole 64-byte sectors, so a wave
-// formed from the pending lists (sparse rounds: lane = pending HRU, 64 different slabs) wastes nothing of what it fetches,
+// formed from the pending list (sparse rounds: lane = pending HRU, several slabs) wastes nothing of what it fetches,
 // while a dense wave still reads its slab front to back (its 16-byte accesses, 64 bytes apart, fill the same lines over four
 // instructions).  Measured, same box: evaluation kernel 6.8 vs 7.7-8.0 ms per step with the sparse rounds starting at 30 %
 // pending instead of 4 %; the opening stage, which WRITES the context, 4.7-4.9 vs 4.3-4.5 ms.  So the slab has two regions:
@@ -130,10 +130,91 @@ struct KArgs {
 // only the two stage kernels exchange (everything after) in pairs.  (G = 16 and 32 measure like 8, G = 4 worse than 2.)
 // (Not kept: one contiguous block per HRU, [hru][word], measured in round 2 against the slabs: sparse rounds -35 %, dense
 // rounds +23 %.)
+// SurfEBConst / SurfEBMut are parked group by group (vic_surface.hpp): word ranges of the groups
+constexpr int EBC_W_POST = offsetof(SurfEBConst, delta_t) / 8, EBC_W_ALWAYS = offsetof(SurfEBConst, ice0) / 8,
+              EBC_W_FROZEN = offsetof(SurfEBConst, kappa_snow) / 8, EBC_W_SNOWCOV = offsetof(SurfEBConst, LongSnowIn) / 8,
+              EBC_W_INCL = offsetof(SurfEBConst, lmoist) / 8, EBC_W_EVAP = offsetof(SurfEBConst, Wdew) / 8,
+              EBC_W_CANOPY = offsetof(SurfEBConst, Cs2) / 8;
+constexpr int EBM_W_FEED = offsetof(SurfEBMut, deltaCC) / 8, EBM_W_IN3 = offsetof(SurfEBMut, Tsnow_surf) / 8,
+              EBM_W_TSNOW = offsetof(SurfEBMut, ra_used) / 8, EBM_W_RA1 = EBM_W_TSNOW + 1, EBM_W_VV = offsetof(SurfEBMut, vv) / 8,
+              EBM_W_KEEP = offsetof(SurfEBMut, Tnew2) / 8;
+static_assert(offsetof(SurfEBMut, fusion) / 8 == EBM_W_IN3 - 1 && offsetof(SurfEBMut, layerevap) / 8 == EBM_W_VV + 3, "SurfEBMut layout");
+constexpr size_t CW_SV = sizeof(SurfSolve) / 8, CW_EBM = sizeof(SurfEBMut) / 8, CW_EBC = EBC_W_CANOPY,      // Cs2 is never parked
+                 CW_P = sizeof(SubStep) / 8, CW_L = sizeof(SubLoop) / 8, CW_C = sizeof(StepConst) / 8;
+constexpr size_t CO_SV = 0, CO_EBM = CO_SV + CW_SV, CO_EBC = CO_EBM + CW_EBM, CO_P = CO_EBC + CW_EBC, CO_L = CO_P + CW_P,
+                 CO_C = CO_L + CW_L, CO_W = CO_C + CW_C;
+constexpr size_t CW_W = sizeof(WCarry) / 8, CO_WM = CO_W + CW_W;
+template <int NN> constexpr size_t ctx_words() { return CO_WM + sizeof(WCarryMulti<NN>) / 8; }
+static_assert(sizeof(StepConstPost) <= sizeof(StepConst), "StepConstPost is parked in StepConst's words");
+// SubLoop in two parts: the head always, the sub-step sums only once a sub-step has been booked (they are zero before)
+constexpr size_t CW_L_HEAD = offsetof(SubLoop, st_AlbedoOver) / 8;
+// SurfSolve: the Brent state and the abscissa (rewritten by every evaluation), then the rest
+constexpr size_t CW_SV_ITER = offsetof(SurfSolve, Tsurf) / 8;
+
 constexpr int CTX_GROUP = 8, CTX_GROUP_B = 2;
-// Word W of HRU g: region A [hru / 64][W / G][hru % 64][G], then region B the same with G_B and W - CTX_NA
 constexpr size_t CTX_NA = sizeof(SurfSolve) / 8 + sizeof(SurfEBMut) / 8 + offsetof(SurfEBConst, Cs2) / 8;
-constexpr size_t CTX_NA_PAD = (CTX_NA + CTX_GROUP - 1) / CTX_GROUP * CTX_GROUP;
+static_assert(CTX_NA == CO_P, "region A of the context slab = what the evaluation kernel reads");
+// Parking map of region A: struct word (CO_SV .. CO_P) -> slab word.  The structs keep their layout; where a word is parked
+// follows who touches it, so that an evaluation of the iteration fetches whole 64-byte sectors it uses and no others.  Every
+// range starts on a sector boundary:
+//   CTXR_ITER    what an evaluation of the iteration rewrites: the Brent state and the abscissa (SurfSolve up to Tsurf)
+//   CTXR_COMMON  what every evaluation reads: the SurfEBMut inputs of the iteration (deltaCC, NetLongSnow, fusion, Tsnow_surf,
+//                ra_used[1]), then SurfEBConst [post] and [always]
+//   CTXR_CLASS   [frozen], [evap], [canopy]: the groups of the common class of a frozen-soil run
+//   CTXR_SNOW    [snowcov], [incl]
+//   CTXR_COLD    what is read and written when the iteration ends or at the final evaluation: the tail of SurfSolve (result,
+//                flags, stage, record bookkeeping) in the first sector, then ra_used[0], [feed] (thin snowpack only) and the
+//                rest of SurfEBMut
+// (The tail of SurfSolve stays among the words an evaluation fetches: surf_solve_consume needs it in the evaluation that ends
+// the iteration, which is not known before the residual is.)
+constexpr int CTXR_ITER = 0, CTXR_COMMON = 16, CTXR_CLASS = 48, CTXR_SNOW = 64, CTXR_COLD = 72, CTXR_END = 104;
+struct CtxMap { unsigned char slab[CTX_NA]; int end[6]; };
+constexpr int ctx_map_run(CtxMap& m, int at, size_t first, size_t last) {      // struct words [first, last) -> slab words from `at`
+  for (size_t w = first; w < last; w++) m.slab[w] = (unsigned char)at++;
+  return at;
+}
+constexpr CtxMap ctx_make_map() {
+  CtxMap m{};
+  int at = ctx_map_run(m, CTXR_ITER, CO_SV, CO_SV + CW_SV_ITER);
+  m.end[0] = at;
+  at = ctx_map_run(m, CTXR_COMMON, CO_EBM + EBM_W_FEED, CO_EBM + EBM_W_TSNOW);
+  at = ctx_map_run(m, at, CO_EBM + EBM_W_RA1, CO_EBM + EBM_W_RA1 + 1);
+  at = ctx_map_run(m, at, CO_EBC, CO_EBC + EBC_W_ALWAYS);
+  m.end[1] = at;
+  at = ctx_map_run(m, CTXR_CLASS, CO_EBC + EBC_W_ALWAYS, CO_EBC + EBC_W_FROZEN);
+  at = ctx_map_run(m, at, CO_EBC + EBC_W_INCL, CO_EBC + EBC_W_CANOPY);
+  m.end[2] = at;
+  at = ctx_map_run(m, CTXR_SNOW, CO_EBC + EBC_W_FROZEN, CO_EBC + EBC_W_INCL);
+  m.end[3] = at;
+  at = ctx_map_run(m, CTXR_COLD, CO_SV + CW_SV_ITER, CO_SV + CW_SV);
+  m.end[4] = at;
+  at = ctx_map_run(m, at, CO_EBM + EBM_W_TSNOW, CO_EBM + EBM_W_TSNOW + 1);
+  at = ctx_map_run(m, at, CO_EBM, CO_EBM + EBM_W_FEED);
+  at = ctx_map_run(m, at, CO_EBM + EBM_W_VV, CO_EBM + CW_EBM);
+  m.end[5] = at;
+  return m;
+}
+constexpr CtxMap CTX_MAP = ctx_make_map();
+constexpr bool ctx_map_is_permutation() {      // every struct word of region A has a slab word of its own
+  bool used[CTXR_END] = {};
+  for (size_t w = 0; w < CTX_NA; w++) {
+    if (CTX_MAP.slab[w] >= CTXR_END || used[CTX_MAP.slab[w]]) return false;
+    used[CTX_MAP.slab[w]] = true;
+  }
+  int n = 0;
+  for (int i = 0; i < CTXR_END; i++) n += used[i] ? 1 : 0;
+  return n == (int)CTX_NA;
+}
+static_assert(ctx_map_is_permutation(), "parking map of region A");
+static_assert(CTXR_ITER % CTX_GROUP == 0 && CTXR_COMMON % CTX_GROUP == 0 && CTXR_CLASS % CTX_GROUP == 0 && CTXR_SNOW % CTX_GROUP == 0
+              && CTXR_COLD % CTX_GROUP == 0 && CTXR_END % CTX_GROUP == 0, "every range of the parking map starts on a sector boundary");
+static_assert(CTX_MAP.end[0] == CTXR_COMMON && CTX_MAP.end[1] <= CTXR_CLASS && CTX_MAP.end[2] <= CTXR_SNOW && CTX_MAP.end[3] <= CTXR_COLD
+              && CTX_MAP.end[4] <= CTXR_COLD + CTX_GROUP && CTX_MAP.end[5] <= CTXR_END && CTXR_END - CTX_MAP.end[5] < CTX_GROUP,
+              "ranges of the parking map; the tail of SurfSolve, which every evaluation fetches, in one sector");
+static_assert(CTX_MAP.end[1] - CTXR_COMMON == 31 && CTX_MAP.end[2] - CTXR_CLASS == 13,
+              "the iteration's inputs: 4 sectors for every class, 2 more for frozen soil / evaporation / canopy");
+// Slab word S of HRU g: region A [hru / 64][S / G][hru % 64][G], then region B the same with G_B and W - CTX_NA
+constexpr size_t CTX_NA_PAD = CTXR_END;
 constexpr size_t ctx_padded_words(size_t words) {      // slab words per lane
   return CTX_NA_PAD + ((words > CTX_NA ? words - CTX_NA : 0) + CTX_GROUP_B - 1) / CTX_GROUP_B * CTX_GROUP_B;
 }
@@ -144,7 +225,10 @@ struct CtxRef {
     return CtxRef{base + (g >> 6) * (ctx_padded_words(words_per_hru) * 64), (int)(g & 63)};
   }
   VIC_DEV unsigned long long* word(size_t W) const {
-    if (W < CTX_NA) return p + (W / CTX_GROUP) * (64 * CTX_GROUP) + lane * CTX_GROUP + (W % CTX_GROUP);
+    if (W < CTX_NA) {
+      const size_t S = CTX_MAP.slab[W];
+      return p + (S / CTX_GROUP) * (64 * CTX_GROUP) + lane * CTX_GROUP + (S % CTX_GROUP);
+    }
     const size_t V = W - CTX_NA;
     return p + CTX_NA_PAD * 64 + (V / CTX_GROUP_B) * (64 * CTX_GROUP_B) + lane * CTX_GROUP_B + (V % CTX_GROUP_B);
   }
@@ -167,27 +251,6 @@ VIC_DEV void ctx_get(const CtxRef& r, size_t word0, T& v) {
   for (int i = 0; i < NW; i++) tmp[i] = *r.word(word0 + i);
   __builtin_memcpy(&v, tmp, sizeof(T));
 }
-// SurfEBConst / SurfEBMut are parked group by group (vic_surface.hpp): word ranges of the groups
-constexpr int EBC_W_POST = offsetof(SurfEBConst, delta_t) / 8, EBC_W_ALWAYS = offsetof(SurfEBConst, ice0) / 8,
-              EBC_W_FROZEN = offsetof(SurfEBConst, kappa_snow) / 8, EBC_W_SNOWCOV = offsetof(SurfEBConst, LongSnowIn) / 8,
-              EBC_W_INCL = offsetof(SurfEBConst, lmoist) / 8, EBC_W_EVAP = offsetof(SurfEBConst, Wdew) / 8,
-              EBC_W_CANOPY = offsetof(SurfEBConst, Cs2) / 8;
-constexpr int EBM_W_FEED = offsetof(SurfEBMut, deltaCC) / 8, EBM_W_IN3 = offsetof(SurfEBMut, Tsnow_surf) / 8,
-              EBM_W_TSNOW = offsetof(SurfEBMut, ra_used) / 8, EBM_W_RA1 = EBM_W_TSNOW + 1, EBM_W_VV = offsetof(SurfEBMut, vv) / 8,
-              EBM_W_KEEP = offsetof(SurfEBMut, Tnew2) / 8;
-static_assert(offsetof(SurfEBMut, fusion) / 8 == EBM_W_IN3 - 1 && offsetof(SurfEBMut, layerevap) / 8 == EBM_W_VV + 3, "SurfEBMut layout");
-constexpr size_t CW_SV = sizeof(SurfSolve) / 8, CW_EBM = sizeof(SurfEBMut) / 8, CW_EBC = EBC_W_CANOPY,      // Cs2 is never parked
-                 CW_P = sizeof(SubStep) / 8, CW_L = sizeof(SubLoop) / 8, CW_C = sizeof(StepConst) / 8;
-constexpr size_t CO_SV = 0, CO_EBM = CO_SV + CW_SV, CO_EBC = CO_EBM + CW_EBM, CO_P = CO_EBC + CW_EBC, CO_L = CO_P + CW_P,
-                 CO_C = CO_L + CW_L, CO_W = CO_C + CW_C;
-constexpr size_t CW_W = sizeof(WCarry) / 8, CO_WM = CO_W + CW_W;
-template <int NN> constexpr size_t ctx_words() { return CO_WM + sizeof(WCarryMulti<NN>) / 8; }
-static_assert(sizeof(StepConstPost) <= sizeof(StepConst), "StepConstPost is parked in StepConst's words");
-static_assert(CTX_NA == CO_P, "region A of the context slab = what the evaluation kernel reads");
-// SubLoop in two parts: the head always, the sub-step sums only once a sub-step has been booked (they are zero before)
-constexpr size_t CW_L_HEAD = offsetof(SubLoop, st_AlbedoOver) / 8;
-// SurfSolve: the Brent state and the abscissa (rewritten by every evaluation), then the rest
-constexpr size_t CW_SV_ITER = offsetof(SurfSolve, Tsurf) / 8;
 
 template <class T>
 VIC_DEV void ctx_put_words(const CtxRef& r, size_t word0, const T& v, int first, int last) {
@@ -881,15 +944,17 @@ struct EArgs {
   int list_cap;
   const int* hkey;
   int* profile_next;     // work-list cursor of the profile kernel, cleared for its next launch
-  int* evalonly;         // HRUs that wait for an evaluation without a solve (final evaluation on record)
-  int* eo_list_next;     // ... and which: with the work list this is every HRU the round leaves pending
-  // sparse rounds (at most list_thr HRUs pending; the others go through glist / map and test hstate): lane = pending HRU, taken
-  // from the work list the profile kernel has just gone through and from the evaluation-only list of the round before
+  // every HRU the round leaves pending -- for a solve, or for an evaluation without one (final evaluation on record) -- also
+  // goes on a flat list: PEND_STRIPES stripes of pend_cap entries, one chunk per wave in lane order (vic_profile.hpp)
+  int* pend_list_next;
+  int* pend_count_next;  // the stripes' fill counters, PEND_CNT_STRIDE apart
+  int pend_cap;
+  // sparse rounds (at most list_thr HRUs pending; the others go through glist / map and test hstate): lane = entry of the flat
+  // list the round before has left.  -1 in the round after a stage kernel, which leaves no flat list.
   int list_thr;
-  const int* list_cur;
-  const int* count_cur;  // [NBUCKET]
-  const int* eo_list_cur;
-  const int* npend_cur;  // their sum + the length of eo_list_cur, written by the round's profile kernel
+  const int* pend_list_cur;
+  const int* pend_prefix; // [PEND_STRIPES + 1] entries before each stripe of pend_list_cur, packed by the round's profile kernel
+  const int* npend_cur;   // the number of evaluations pending, written by the round's profile kernel
   int implicit;          // IMPLICIT: the final evaluation is always solved again (its fallback flags depend on the solves before it)
   const double* veglib;  // for the table-derived part of the residual's inputs (surf_cell_fill)
   const double* forcing; // this step
@@ -900,31 +965,27 @@ constexpr int EVAL_WAVES = 2;
 __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void vic_surf_eval(const EArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *a.profile_next = 0;
   // Sparse rounds.  A dense launch pays a whole wave -- its chain of dependent loads -- for every 64 HRUs of which one is
-  // pending.  The number pending is on the device before the host knows it (the work list the profile kernel has just gone
-  // through + the evaluation-only list of the round before), so every wave looks at it: from the round in which at most
-  // list_thr HRUs are pending, lane = entry of those lists and the waves beyond the lists' end leave at once.
+  // pending.  The number pending is on the device before the host knows it (the flat list the round before has left), so
+  // every wave looks at it: from the round in which at most list_thr HRUs are pending, lane = entry of that list and the
+  // waves beyond its end leave at once.  The entry's stripe is found by bisection of the packed prefix array; 64 consecutive
+  // entries of a stripe come from about 1 / (fraction pending) producing waves, so a list-formed wave reads a few context slabs.
   const int npend = *a.npend_cur;
   int g;
   if (npend <= a.list_thr) {
     if ((int)blockIdx.x * 64 >= npend) return;
-    __shared__ int bcount[NBUCKET];
-    for (int b = threadIdx.x; b < NBUCKET; b += 64) bcount[b] = a.count_cur[b];
+    __shared__ int prefix[PEND_STRIPES + 1];
+    for (int b = threadIdx.x; b < PEND_STRIPES + 1; b += 64) prefix[b] = a.pend_prefix[b];
     __syncthreads();
-    int nsolve = 0;
-#pragma unroll 1
-    for (int b = 0; b < NBUCKET; b++) nsolve += bcount[b];
     const int gi = blockIdx.x * 64 + threadIdx.x;
     if (gi >= npend) return;
-    if (gi < nsolve) {
-      int rem = gi, found = 0;
-#pragma unroll 1
-      for (int b = 0; b < NBUCKET; b++) {
-        const int cb = bcount[b];
-        if (rem < cb) { found = b * a.list_cap + rem; break; }
-        rem -= cb;
-      }
-      g = a.list_cur[found];
-    } else g = a.eo_list_cur[gi - nsolve];
+    int lo = 0, hi = PEND_STRIPES;             // prefix[lo] <= gi < prefix[hi]
+#pragma unroll
+    for (int it = 0; it < 6; it++) {
+      const int mid = (lo + hi) >> 1;
+      const bool up = prefix[mid] <= gi;
+      lo = up ? mid : lo; hi = up ? hi : mid;
+    }
+    g = a.pend_list_cur[(size_t)lo * a.pend_cap + (gi - prefix[lo])];
   } else {
     const int gi = a.map.index(blockIdx.x, threadIdx.x, a.gcount);
     if (gi < 0) return;
@@ -1021,14 +1082,15 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void v
   else if (need_solve) { a.ts[g] = sv.x; a.pslot[g] = slot ^ 1; }     // keep the record just used, overwrite the older one
   list_append(a.list_next, a.count_next, a.list_cap, need_solve, a.hkey[g], g);
   {
-    const bool eo = sv.stage != SurfSolve::DONE && !need_solve;
-    const unsigned long long m = __ballot(eo);
+    // the flat list: one chunk per wave, one atomic on the stripe's own line
+    const bool pend = sv.stage != SurfSolve::DONE;
+    const unsigned long long m = __ballot(pend);
     if (m != 0) {
-      const int lane = (int)__lane_id(), lead = __ffsll((long long)m) - 1;
+      const int lane = (int)__lane_id(), lead = __ffsll((long long)m) - 1, stripe = blockIdx.x % PEND_STRIPES;
       int base = 0;
-      if (lane == lead) base = atomicAdd(a.evalonly, __popcll(m));
+      if (lane == lead) base = atomicAdd(a.pend_count_next + stripe * PEND_CNT_STRIDE, __popcll(m));
       base = __shfl(base, lead);
-      if (eo) a.eo_list_next[base + __popcll(m & ((1ull << lane) - 1ull))] = g;
+      if (pend) a.pend_list_next[(size_t)stripe * a.pend_cap + base + __popcll(m & ((1ull << lane) - 1ull))] = g;
     }
   }
 }
@@ -1368,9 +1430,10 @@ struct FdChunk {
   LaunchMap map;                   // XCD-aware launch order when the chunk's list is regular (slot-major, every slot ccount cells)
   DevBuf<int> d_list[2];           // work lists (HRU ids)
   DevBuf<int> d_fb_list, d_fb_count;   // IMPLICIT: HRUs whose Newton iteration failed this round
-  DevBuf<int> d_count;             // counter block (CNT_*): segment sizes of the two lists, profile cursor, evaluation-only counts, pending total
-  DevBuf<int> d_elist[2];          // evaluation-only lists (flat, gcount entries): pending HRUs that need no solve
+  DevBuf<int> d_count;             // counter block (CNT_*): segment sizes of the two lists, profile cursor, pending total and prefix, stripe fills
+  DevBuf<int> d_plist[2];          // flat pending lists: PEND_STRIPES stripes of pend_cap entries
   int list_cap = 0;                // entries per segment
+  int pend_cap = 0;                // entries per stripe
   PinnedBuf<int> h_count;          // pinned read-back, RB_DEPTH slots of CNT_TOTAL
   Stream stream;
   Event done, readback[RB_DEPTH];
@@ -1433,7 +1496,7 @@ struct vicgpu_ctx {
   int write_fluxes = 1;
   int steps_done = 0;
   int profile_waves = 0;           // resident waves of the profile kernel
-  int eval_list_pct = 30;          // sparse evaluation rounds (lane = pending HRU) once at most this percentage of the HRUs is pending
+  int eval_list_pct = 75;          // sparse evaluation rounds (lane = pending HRU) once at most this percentage of the HRUs is pending
   bool node_newton = false;        // frozen-node root finder: safeguarded Newton instead of the reference's Brent iteration
   int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
   int out_step_ratio = 1;
@@ -1504,21 +1567,30 @@ static int profile_resident_waves(int device, bool newton) {
 // Counter block of a chunk.  Every group sits on its own 128-byte lines: the evaluation kernel's waves all read the pending
 // count while others append to the next list with atomics, and reads that share a line with those atomics queue behind them
 // in the L2 channel (measured: the dense evaluation rounds went from 0.6 to 1.4-2.5 ms when they did).
-constexpr int CNT_LIST_STRIDE = 64, CNT_CURSOR = 128, CNT_EVALONLY = 160, CNT_EVALONLY_STRIDE = 32, CNT_NPEND = 224, CNT_TOTAL = 256;
-static_assert(NBUCKET <= CNT_LIST_STRIDE, "counter block layout");
+// The fill counters of the flat pending lists' stripes take a line each (one shared address cost 0.8 ms per step); the
+// evaluation waves read the packed prefix of the current list, on lines nobody appends to.  The whole block is read back.
+constexpr int CNT_LIST_STRIDE = 64, CNT_CURSOR = 128, CNT_NPEND = 160, CNT_PREFIX = 192, CNT_STRIPES = 288,
+              CNT_STRIPES_STRIDE = PEND_STRIPES * PEND_CNT_STRIDE, CNT_TOTAL = CNT_STRIPES + 2 * CNT_STRIPES_STRIDE;
+static_assert(NBUCKET <= CNT_LIST_STRIDE && CNT_PREFIX + PEND_STRIPES + 1 <= CNT_STRIPES && CNT_STRIPES % 32 == 0, "counter block layout");
 static inline int* cnt_list(int* d_count, int l) { return d_count + l * CNT_LIST_STRIDE; }
-static inline int* cnt_evalonly(int* d_count, int l) { return d_count + CNT_EVALONLY + l * CNT_EVALONLY_STRIDE; }
+static inline int* cnt_stripes(int* d_count, int l) { return d_count + CNT_STRIPES + l * CNT_STRIPES_STRIDE; }
+// entries of flat list `l` in a read-back copy of the block
+static inline int cnt_pending(const int* h_count, int l) {
+  int n = 0;
+  for (int s = 0; s < PEND_STRIPES; s++) n += h_count[CNT_STRIPES + l * CNT_STRIPES_STRIDE + s * PEND_CNT_STRIDE];
+  return n;
+}
 
 // One model step of the finite-difference pipeline for one chunk (see the header of this file).  Blocks the calling
 // host thread: the number of Brent rounds is data dependent, so the pending count is read back once the first rounds
 // are through.
-static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* nevalonly) {
+static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* npending) {
   HIPCHK(ch, hipMemcpyAsync(ch->h_count, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, ch->stream));
   HIPCHK(ch, hipStreamSynchronize(ch->stream));
   int n = 0;
   for (int b = 0; b < NBUCKET; b++) n += ch->h_count[which * CNT_LIST_STRIDE + b];
   *nsolve = n;
-  *nevalonly = ch->h_count[CNT_EVALONLY + which * CNT_EVALONLY_STRIDE];
+  *npending = cnt_pending(ch->h_count, which);
   return VICGPU_OK;
 }
 
@@ -1543,7 +1615,8 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
   ea.cell_params = c->dom.d_cp; ea.hpi = c->dom.d_hpi; ea.ctx = c->dom.d_ctx;
   ea.ctx_words = NODE_DISPATCH(Nn, ctx_words);
   ea.pout = c->dom.d_pout; ea.pslot = c->dom.d_pslot; ea.ts = c->dom.d_ts; ea.hstate = c->dom.d_hstate; ea.profile_next = ch->d_count + CNT_CURSOR;
-  ea.list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
+  const int list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
+  ea.pend_cap = ch->pend_cap;
   ea.list_cap = ch->list_cap; ea.hkey = c->dom.d_hkey; ea.implicit = c->o.IMPLICIT; ea.jl = c->dom.d_jl;
   ea.veglib = c->d_veglib; ea.forcing = ka.forcing; ea.month = ka.dmy.month;
   const bool trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
@@ -1556,8 +1629,8 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
     int rb_first = -1;                         // first round whose counts were read back
     for (int round = 0;; round++) {
       pa.list = ch->d_list[cur]; pa.count = cnt_list(ch->d_count, cur); pa.count_zero = cnt_list(ch->d_count, cur ^ 1);
-      pa.evalonly_zero = cnt_evalonly(ch->d_count, cur ^ 1);
-      pa.pend_counts = cnt_list(ch->d_count, cur); pa.pend_eo = cnt_evalonly(ch->d_count, cur); pa.pend_out = ch->d_count + CNT_NPEND;
+      pa.pend_counts = cnt_list(ch->d_count, cur); pa.pend_stripes = cnt_stripes(ch->d_count, cur);
+      pa.pend_stripes_zero = cnt_stripes(ch->d_count, cur ^ 1); pa.pend_prefix = ch->d_count + CNT_PREFIX; pa.pend_out = ch->d_count + CNT_NPEND;
       if (c->o.IMPLICIT) {
         // the Newton iteration for every listed HRU; those it fails for go on the fall-back list, which the explicit kernel
         // (the same one, on that list) solves right after (func_surf_energy_bal.c:192-222)
@@ -1577,19 +1650,19 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       }
       HIPCHK(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
       ea.list_next = ch->d_list[cur ^ 1]; ea.count_next = cnt_list(ch->d_count, cur ^ 1);
-      ea.evalonly = cnt_evalonly(ch->d_count, cur ^ 1); ea.eo_list_next = ch->d_elist[cur ^ 1];
-      ea.list_cur = ch->d_list[cur]; ea.count_cur = cnt_list(ch->d_count, cur);
-      ea.eo_list_cur = ch->d_elist[cur]; ea.npend_cur = ch->d_count + CNT_NPEND;
-      // the device switches to the lists by itself; once the host knows (RB_LAG rounds late) that it has, the grid shrinks too
+      ea.pend_list_next = ch->d_plist[cur ^ 1]; ea.pend_count_next = cnt_stripes(ch->d_count, cur ^ 1);
+      ea.pend_list_cur = ch->d_plist[cur]; ea.pend_prefix = ch->d_count + CNT_PREFIX; ea.npend_cur = ch->d_count + CNT_NPEND;
+      ea.list_thr = round > 0 ? list_thr : -1;      // the stage kernel before round 0 fills the keyed list only
+      // the device switches to the list by itself; once the host knows (RB_LAG rounds late) that it has, the grid shrinks too
       const bool sparse = npend >= 0 && npend <= ea.list_thr;
       hipLaunchKernelGGL(vic_surf_eval, dim3(sparse ? ((npend + 63) / 64 > 0 ? (npend + 63) / 64 : 1) : ea.map.nblocks(ch->gcount)), dim3(64), 0, st, ea);
       HIPCHK(ch, hipGetLastError());
       cur ^= 1;
       ch->rounds++;
       if (trace_rounds) {       // tuning: what every round leaves pending (a host round trip per round)
-        int n = 0, ne = 0;
-        if (fd_read_count(ch, cur, &n, &ne) != VICGPU_OK) return VICGPU_ERR_HIP;
-        fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->dom.chunks[0]), p, round, n, ne, ch->gcount);
+        int n = 0, np = 0;
+        if (fd_read_count(ch, cur, &n, &np) != VICGPU_OK) return VICGPU_ERR_HIP;
+        fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->dom.chunks[0]), p, round, n, np - n, ch->gcount);
       }
       // The list sizes of this round travel to the host behind the kernels just launched; the host looks at the copy issued
       // RB_LAG rounds ago, which has long arrived, so waiting for it never leaves the GPU idle.  The counts only shrink from
@@ -1607,10 +1680,10 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
         const int* h = ch->h_count + slot * CNT_TOTAL;
         int n = 0;
         for (int b = 0; b < NBUCKET; b++) n += h[rb_list[slot] * CNT_LIST_STRIDE + b];
-        const int neo = h[CNT_EVALONLY + rb_list[slot] * CNT_EVALONLY_STRIDE];
-        if (n == 0 && neo == 0) break;
+        const int np = cnt_pending(h, rb_list[slot]);      // solves + final evaluations on record
+        if (np == 0) break;
         nmax = n;
-        npend = n + neo;
+        npend = np;
       }
     }
     ka.phase = p; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur);
@@ -1912,8 +1985,11 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
       HIPCHK(c, ch.d_list[0].alloc(gn * NBUCKET));
       HIPCHK(c, ch.d_list[1].alloc(gn * NBUCKET));
       HIPCHK(c, ch.d_count.alloc(CNT_TOTAL));
-      HIPCHK(c, ch.d_elist[0].alloc(gn));
-      HIPCHK(c, ch.d_elist[1].alloc(gn));
+      // a wave appends at most 64 entries to stripe blockIdx.x % PEND_STRIPES, and no evaluation grid is larger than the dense one
+      ch.pend_cap = 64 * ((ch.map.nblocks(ch.gcount) + PEND_STRIPES - 1) / PEND_STRIPES);
+      if (ch.pend_cap < 64) ch.pend_cap = 64;
+      HIPCHK(c, ch.d_plist[0].alloc((size_t)ch.pend_cap * PEND_STRIPES));
+      HIPCHK(c, ch.d_plist[1].alloc((size_t)ch.pend_cap * PEND_STRIPES));
       if (c->o.IMPLICIT) {
         HIPCHK(c, ch.d_fb_list.alloc(gn * NBUCKET));
         HIPCHK(c, ch.d_fb_count.alloc(NBUCKET + 1));
