@@ -1,4 +1,4 @@
-// hip/hip_runtime.h stand-in for the SANITIZER build of vic_amd/csrc/vicgpu_api.hip (tools/hostemu/build.sh).
+// hip/hip_runtime.h stand-in for the SANITIZER build of vic_amd/csrc/vicgpu_api.hip and the headers it includes (tools/hostemu/build.sh).
 //
 // Test infrastructure only.  GPU AddressSanitizer is not available on the MI355X pool, so to put the device code under
 // ASan / UBSan the translation unit is compiled as plain C++ for the host with this header first on the include path:

@@ -1,13 +1,23 @@
 // vic_group.hpp — the device group of include/vicgpu_group.h: N shard contexts of one domain, stepped at the same time.
 //
-// Host code only, included at the end of vicgpu_api.hip: it builds on the single-context entries and on their pitched
-// variants (prefetch_impl, get_outputs_impl, glacier_fit_impl, d2h_cols), which copy one shard's columns straight between
-// the device and the caller's global [..][ncell] table.  No kernel lives here.
+// Host code only: it builds on the single-context entries of include/vicgpu.h and on their pitched variants declared below,
+// which copy one shard's columns straight between the device and the caller's global [..][ncell] table.  No kernel lives here.
 #pragma once
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
 #include "vicgpu_group.h"
+#include "vic_pipeline.hpp"
+
+// static helpers of vicgpu_api.hip (ld: cells per row of the caller's table)
+static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
+                         const int* dmy, double min_wind, int plapse, int ld);
+static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
+static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
+static int d2h_cols(vicgpu_ctx* c, void* dst, int ld, const void* src, size_t elem, int nrow);
 
 // One persistent host thread per shard.  run(fn) calls fn(k) on thread k for every shard and returns when all have returned.
 // Each thread selects its shard's device once at start (every library entry selects it again anyway).

@@ -1,4 +1,4 @@
-// vic_host.hpp — owners of the runtime objects of the host layer (vicgpu_api.hip, vic_group.hpp).  Host code only, no kernels.
+// vic_host.hpp — owners of the runtime objects of the host layer (vic_pipeline.hpp, vicgpu_api.hip, vic_group.hpp).  Host code only, no kernels.
 // Move-only handles: each releases what it holds in its destructor, so an entry point that returns early and a context that
 // is deleted half-built leave nothing behind.  Creation returns the runtime's error code; nothing throws.  The buffers
 // convert to the raw pointer, so the kernel-argument structs and the runtime calls take them as they took the pointers.

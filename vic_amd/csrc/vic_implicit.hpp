@@ -177,7 +177,6 @@ struct ImplicitSolver {
 
 }  // namespace vic
 
-// included by vicgpu_api.hip after its list_append
 __global__ __launch_bounds__(64) void vic_profile_solve_implicit(const vic::PArgs a, const vic::IArgs x) {
   using namespace vic;
   __shared__ int bcount[NBUCKET];

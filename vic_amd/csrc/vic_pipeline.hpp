@@ -1,0 +1,423 @@
+// vic_pipeline.hpp — the host pipeline: the context (vicgpu_ctx), what lives as long as a domain (Domain, FdChunk), the
+// kernel-argument structs filled from them, the launchers, and the step of the finite-difference pipeline (fd_step: the
+// round loop; fd_chunk_run: all steps of one vicgpu_step call for one cell chunk).  Host code only, no kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+#include "vicgpu.h"
+#include "vic_profile.hpp"
+#include "vic_putdata.hpp"
+#include "vic_host.hpp"
+#include "vic_implicit.hpp"
+#include "vic_ctx.hpp"
+#include "vic_hru_io.hpp"
+#include "vic_kernels.hpp"
+#include "vic_aux_kernels.hpp"
+
+using namespace vic;
+
+#define HIPIGN(call) do { hipError_t ign_ = (call); (void)ign_; } while (0)
+#define HIPCHK(ctx, call)                                                                              \
+  do {                                                                                                 \
+    hipError_t e_ = (call);                                                                            \
+    if (e_ != hipSuccess) {                                                                            \
+      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                  \
+      return VICGPU_ERR_HIP;                                                                           \
+    }                                                                                                  \
+  } while (0)
+
+// Host <-> device copies and fills of the set-up and read-back calls go through the context's own (non-blocking) stream
+// and are waited for there: a copy on the null stream is not ordered against kernels on a non-blocking stream, and a
+// pageable host-to-device copy may return before its last bytes have landed in device memory.
+static hipError_t copy_on(hipStream_t st, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+static hipError_t fill_on(hipStream_t st, void* dst, int value, size_t bytes) {
+  hipError_t e = hipMemsetAsync(dst, value, bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+
+// ------------------------------------------------------------------------------------------------ context
+// A chunk of cells with all their HRUs.  Cells never interact, so every chunk runs the whole step sequence on its own
+// stream, driven by its own host thread: while one chunk is in the thin tail of its Brent rounds (a few stragglers,
+// latency bound) or in a stage kernel (memory / latency bound), the profile solves of the others fill the SIMDs.
+// The host reads the round's list sizes back RB_LAG rounds late (fd_step): it stays that many rounds ahead of the device, so the
+// thin tail rounds -- two short kernels each -- never wait for a host round trip; the price is RB_LAG rounds on empty lists at
+// the end of the iteration (both kernels return at once).
+constexpr int RB_LAG = 3, RB_DEPTH = RB_LAG + 1;
+struct FdChunk {
+  int c0 = 0, ccount = 0;          // cells [c0, c0 + ccount)
+  DevBuf<int> d_glist;             // their HRUs, ascending
+  int gcount = 0;
+  LaunchMap map;                   // XCD-aware launch order when the chunk's list is regular (slot-major, every slot ccount cells)
+  DevBuf<int> d_list[2];           // work lists (HRU ids)
+  DevBuf<int> d_fb_list, d_fb_count;   // IMPLICIT: HRUs whose Newton iteration failed this round
+  DevBuf<int> d_count;             // counter block (CNT_*): segment sizes of the two lists, profile cursor, pending total and prefix, stripe fills
+  DevBuf<int> d_plist[2];          // flat pending lists: PEND_STRIPES stripes of pend_cap entries
+  int list_cap = 0;                // entries per segment
+  int pend_cap = 0;                // entries per stripe
+  PinnedBuf<int> h_count;          // pinned read-back, RB_DEPTH slots of CNT_TOTAL
+  Stream stream;
+  Event done, readback[RB_DEPTH];
+  std::string err;
+  int status = 0;
+  long long rounds = 0, steps = 0;
+};
+
+// Everything that lives exactly as long as a domain: vicgpu_set_domain builds it, free_domain drops it as a whole
+struct Domain {
+  int ncell = 0, nhru = 0;
+  bool domain_ready = false;       // set at the end of a successful vicgpu_set_domain
+  bool any_glacier = false;
+  DevBuf<double> d_cp, d_hpd, d_sd, d_flux, d_cell_out, d_accum;
+  DevBuf<int> d_hpi, d_si, d_cell_off, d_cell_list, d_hru_err, d_cell_err;
+  // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
+  bool fd = false;
+  DevBuf<unsigned long long> d_ctx;
+  DevBuf<double> d_pin, d_ts, d_pout;
+  DevBuf<int> d_hstate, d_pslot, d_hkey, d_lastexp, d_jl;
+  DevBuf<double> d_pimp;           // IMPLICIT only
+  std::vector<FdChunk> chunks;     // cell chunks, each an independent pipeline on its own stream
+  // put_data (vicgpu_out.h): output tables [nrow][ncell], allocated by vicgpu_put_data_config
+  bool put_on = false;
+  int out_nrow = 0;
+  OutLayout out_lay;
+  DevBuf<double> d_out_data, d_out_agg, d_pb;
+  DevBuf<unsigned char> d_rowagg;  // [out_nrow] aggregation type of every output row
+};
+
+struct vicgpu_ctx {
+  vicgpu_options opt;
+  Opt o;
+  int device;
+  std::string err;
+  int nveg_rows = 0;
+  DevBuf<double> d_veglib;
+  Domain dom;
+  // forcing: d_forcing / d_snowflag / dmy / chunk_steps describe the CURRENT chunk = slot[cur] (views into the slot, which
+  // owns the memory and outlives a domain); the other slot takes the prefetch of the next one (vicgpu_prefetch_forcing*,
+  // vicgpu_swap_forcing)
+  double* d_forcing = nullptr;
+  unsigned char* d_snowflag = nullptr;
+  std::vector<int> dmy;            // host copy [nsteps][VIC_NDMY]
+  int chunk_steps = 0;
+  struct ForcingSlot {
+    DevBuf<double> d_f, d_raw;
+    DevBuf<unsigned char> d_s;
+    PinnedBuf<char> h_stage;       // pinned staging for pageable sources
+    std::vector<int> dmy;
+    int nsteps = 0;
+    Event uploaded;                // copy stream: the chunk is in the slot
+    Event released;                // context stream: every step that read the slot has been queued before it
+    bool upload_pending = false, was_current = false;
+  } slot[2];
+  int cur = -1, staged = -1;
+  Stream stream, copy_stream;      // `stream` may be borrowed (vicgpu_set_stream)
+  std::vector<Event> ev;           // start/stop pairs of the last vicgpu_step call
+  int ev_used = 0;
+  int write_fluxes = 1;
+  int steps_done = 0;
+  int profile_waves = 0;           // resident waves of the profile kernel
+  int eval_list_pct = 75;          // sparse evaluation rounds (lane = pending HRU) once at most this percentage of the HRUs is pending
+  bool node_newton = false;        // frozen-node root finder: safeguarded Newton instead of the reference's Brent iteration
+  int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
+  int out_step_ratio = 1;
+};
+
+static void free_domain(vicgpu_ctx* c) {
+  c->dom = Domain();
+  c->chunk_steps = 0;              // a forcing chunk belongs to the domain it was pushed for (its rows are ncell wide)
+  c->dmy.clear();
+  c->cur = c->staged = -1;
+  c->d_forcing = nullptr; c->d_snowflag = nullptr;
+}
+
+template <int NN>
+static hipError_t launch_hru(const KArgs& ka, hipStream_t st, bool ordinary, bool glacier) {
+  const int nblk = ka.map.nblocks(ka.gcount);
+  // ordinary HRUs run the monolithic kernel with QUICK_FLUX only (Nnode == 3); the other node counts never instantiate it
+  if constexpr (NN == 3) {
+    if (ordinary) hipLaunchKernelGGL((vic_hru_step<NN, false>), dim3(nblk), dim3(64), 0, st, ka);
+  }
+  if (glacier) hipLaunchKernelGGL((vic_hru_step<NN, true>), dim3(nblk), dim3(64), 0, st, ka);
+  return hipGetLastError();
+}
+
+template <int NN>
+static hipError_t launch_fd_stage(const KArgs& ka, bool multi, hipStream_t st) {
+  const dim3 grid(ka.map.nblocks(ka.gcount)), block(64);
+  if (ka.phase == 0) {
+    if (multi) hipLaunchKernelGGL((vic_fd_stage<NN, true, true>), grid, block, 0, st, ka);
+    else hipLaunchKernelGGL((vic_fd_stage<NN, true, false>), grid, block, 0, st, ka);
+  } else {
+    if (multi) hipLaunchKernelGGL((vic_fd_stage<NN, false, true>), grid, block, 0, st, ka);
+    else hipLaunchKernelGGL((vic_fd_stage<NN, false, false>), grid, block, 0, st, ka);
+  }
+  return hipGetLastError();
+}
+
+// The profile kernel of a node count: 10 nodes have the register-resident instantiation, every other count a generic one
+using ProfileKernel = void (*)(const PArgs);
+template <int NN>
+constexpr ProfileKernel profile_kernel(bool newton) {
+  if constexpr (NN == 10) return newton ? vic_profile_solve_reg<NN, true> : vic_profile_solve_reg<NN, false>;
+  else return newton ? vic_profile_solve_lockstep<NN, true> : vic_profile_solve_lockstep<NN, false>;
+}
+
+template <int NN>
+static hipError_t launch_profile(const PArgs& pa, int nmax, int resident_waves, bool newton, hipStream_t st) {
+  int nblk = (nmax + 63) / 64;
+  if (nblk > resident_waves) nblk = resident_waves;      // persistent waves pull from the work list
+  if (nblk < 1) nblk = 1;                                // block 0 also clears the counters of the round
+  hipLaunchKernelGGL(profile_kernel<NN>(newton), dim3(nblk), dim3(64), 0, st, pa);
+  return hipGetLastError();
+}
+
+template <int NN>
+static int profile_resident_waves(int device, bool newton) {
+  int per_cu = 0, ncu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, profile_kernel<NN>(newton), 64, 0);
+  if (e != hipSuccess || per_cu <= 0) per_cu = 8;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256;
+  return per_cu * ncu;
+}
+
+// Counter block of a chunk.  Every group sits on its own 128-byte lines: the evaluation kernel's waves all read the pending
+// count while others append to the next list with atomics, and reads that share a line with those atomics queue behind them
+// in the L2 channel (measured: the dense evaluation rounds went from 0.6 to 1.4-2.5 ms when they did).
+// The fill counters of the flat pending lists' stripes take a line each (one shared address cost 0.8 ms per step); the
+// evaluation waves read the packed prefix of the current list, on lines nobody appends to.  The whole block is read back.
+constexpr int CNT_LIST_STRIDE = 64, CNT_CURSOR = 128, CNT_NPEND = 160, CNT_PREFIX = 192, CNT_STRIPES = 288,
+              CNT_STRIPES_STRIDE = PEND_STRIPES * PEND_CNT_STRIDE, CNT_TOTAL = CNT_STRIPES + 2 * CNT_STRIPES_STRIDE;
+static_assert(NBUCKET <= CNT_LIST_STRIDE && CNT_PREFIX + PEND_STRIPES + 1 <= CNT_STRIPES && CNT_STRIPES % 32 == 0, "counter block layout");
+static inline int* cnt_list(int* d_count, int l) { return d_count + l * CNT_LIST_STRIDE; }
+static inline int* cnt_stripes(int* d_count, int l) { return d_count + CNT_STRIPES + l * CNT_STRIPES_STRIDE; }
+// entries of flat list `l` in a read-back copy of the block
+static inline int cnt_pending(const int* h_count, int l) {
+  int n = 0;
+  for (int s = 0; s < PEND_STRIPES; s++) n += h_count[CNT_STRIPES + l * CNT_STRIPES_STRIDE + s * PEND_CNT_STRIDE];
+  return n;
+}
+
+// One model step of the finite-difference pipeline for one chunk (see the header of this file).  Blocks the calling
+// host thread: the number of Brent rounds is data dependent, so the pending count is read back once the first rounds
+// are through.
+static int fd_read_count(FdChunk* ch, int which, int* nsolve, int* npending) {
+  HIPCHK(ch, hipMemcpyAsync(ch->h_count, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, ch->stream));
+  HIPCHK(ch, hipStreamSynchronize(ch->stream));
+  int n = 0;
+  for (int b = 0; b < NBUCKET; b++) n += ch->h_count[which * CNT_LIST_STRIDE + b];
+  *nsolve = n;
+  *npending = cnt_pending(ch->h_count, which);
+  return VICGPU_OK;
+}
+
+// F<NN>(args) for the instantiation node count Nnode runs on (node_bound: 10, VIC_MID_NODES or VIC_MAX_NODES)
+#define NODE_DISPATCH(Nnode, F, ...)                                                                                          \
+  (node_bound(Nnode) == 10 ? F<10>(__VA_ARGS__)                                                                           \
+                           : node_bound(Nnode) == VIC_MID_NODES ? F<VIC_MID_NODES>(__VA_ARGS__) : F<VIC_MAX_NODES>(__VA_ARGS__))
+
+// The kernel-argument structs, as far as a domain (and a chunk of it) decides them; the rest stays zero for those who know it:
+// the chunk's HRU list (fd_chunk_run), the step's forcing and date (set_step_inputs), the round's work lists and phase (fd_step).
+static KArgs make_kargs(const vicgpu_ctx* c) {
+  const Domain& d = c->dom;
+  KArgs ka{};
+  ka.o = c->o; ka.ncell = d.ncell; ka.nhru = d.nhru; ka.gcount = d.nhru; ka.nveg_rows = c->nveg_rows;
+  ka.write_fluxes = (c->write_fluxes || d.put_on) ? 1 : 0;      // put_data reads every row of the flux table
+  ka.veglib = c->d_veglib; ka.cell_params = d.d_cp; ka.hpi = d.d_hpi; ka.hpd = d.d_hpd; ka.sd = d.d_sd; ka.si = d.d_si; ka.flux = d.d_flux;
+  ka.hru_err = d.d_hru_err; ka.ctx = d.d_ctx; ka.pin = d.d_pin; ka.ts = d.d_ts; ka.pout = d.d_pout; ka.pslot = d.d_pslot;
+  ka.hstate = d.d_hstate; ka.hkey = d.d_hkey; ka.pimp = d.d_pimp; ka.lastexp = d.d_lastexp; ka.jl = d.d_jl;
+  return ka;
+}
+static CArgs make_cargs(const vicgpu_ctx* c) {
+  const Domain& d = c->dom;
+  CArgs ca{};
+  ca.ncell = d.ncell; ca.nhru = d.nhru; ca.ccount = d.ncell; ca.cell_off = d.d_cell_off; ca.cell_list = d.d_cell_list; ca.hpd = d.d_hpd;
+  ca.hpi_glac = d.d_hpi + (size_t)HPI_IS_GLACIER * d.nhru; ca.flux = d.d_flux; ca.sd = d.d_sd; ca.hru_err = d.d_hru_err;
+  ca.cell_out = d.d_cell_out; ca.accum = d.d_accum; ca.cell_err = d.d_cell_err;
+  return ca;
+}
+static PArgs profile_args(const vicgpu_ctx* c, const FdChunk* ch) {
+  const Domain& d = c->dom;
+  PArgs pa{};
+  pa.pin = d.d_pin; pa.ts = d.d_ts; pa.pout = d.d_pout; pa.pslot = d.d_pslot; pa.jl = d.d_jl; pa.cap = ch->list_cap;
+  pa.Nn = c->o.Nnode; pa.NOFLUX = c->o.NOFLUX; pa.EXP_TRANS = c->o.EXP_TRANS; pa.TFALLBACK = c->o.TFALLBACK;
+  pa.next = ch->d_count + CNT_CURSOR; pa.pend_prefix = ch->d_count + CNT_PREFIX; pa.pend_out = ch->d_count + CNT_NPEND;
+  return pa;
+}
+// ka: the step's stage-kernel arguments, for the forcing rows and the month
+static EArgs eval_args(const vicgpu_ctx* c, const FdChunk* ch, const KArgs& ka) {
+  const Domain& d = c->dom;
+  EArgs ea{};
+  ea.o = c->o; ea.ncell = d.ncell; ea.nhru = d.nhru; ea.Nn = c->o.Nnode; ea.glist = ch->d_glist; ea.gcount = ch->gcount; ea.map = ch->map;
+  ea.cell_params = d.d_cp; ea.hpi = d.d_hpi; ea.ctx = d.d_ctx; ea.ctx_words = NODE_DISPATCH(c->o.Nnode, ctx_words);
+  ea.pout = d.d_pout; ea.pslot = d.d_pslot; ea.ts = d.d_ts; ea.jl = d.d_jl; ea.hstate = d.d_hstate; ea.hkey = d.d_hkey;
+  ea.list_cap = ch->list_cap; ea.pend_cap = ch->pend_cap; ea.profile_next = ch->d_count + CNT_CURSOR;
+  ea.pend_prefix = ch->d_count + CNT_PREFIX; ea.npend_cur = ch->d_count + CNT_NPEND; ea.implicit = c->o.IMPLICIT;
+  ea.veglib = c->d_veglib; ea.forcing = ka.forcing; ea.month = ka.dmy.month;
+  return ea;
+}
+static IArgs implicit_args(const vicgpu_ctx* c, const FdChunk* ch) {
+  const Domain& d = c->dom;
+  IArgs ia{};
+  ia.ncell = d.ncell; ia.nhru = d.nhru; ia.Nband = c->o.Nband; ia.pimp = d.d_pimp; ia.hpi = d.d_hpi; ia.cell_params = d.d_cp;
+  ia.hkey = d.d_hkey; ia.lastexp = d.d_lastexp; ia.fb_list = ch->d_fb_list; ia.fb_count = ch->d_fb_count; ia.cursor = ch->d_fb_count + NBUCKET;
+  return ia;
+}
+
+static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
+  const int Nn = c->o.Nnode;
+  hipStream_t st = ch->stream;
+  if (c->dom.any_glacier) HIPCHK(ch, NODE_DISPATCH(Nn, launch_hru, ka, st, false, true));
+  HIPCHK(ch, hipMemsetAsync(ch->d_count, 0, sizeof(int) * CNT_TOTAL, st));
+  int cur = 0;
+  ka.phase = 0; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur); ka.list_cap = ch->list_cap;
+  HIPCHK(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
+  PArgs pa = profile_args(c, ch);
+  EArgs ea = eval_args(c, ch, ka);
+  const IArgs ia = c->o.IMPLICIT ? implicit_args(c, ch) : IArgs{};      // the fall-back lists exist with IMPLICIT only
+  const int list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
+  const bool trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
+  const int FREE_ROUNDS = 6;       // a Brent solve needs two bracket evaluations, a few iterations and the final evaluation
+  const int nsub = c->o.NF;
+  for (int p = 1; p <= nsub; p++) {
+    int nmax = ch->gcount;
+    int npend = -1;                            // upper bound of the evaluations pending (solves + on-record finals), once known
+    int rb_list[RB_DEPTH];                     // the list each read-back slot counts
+    int rb_first = -1;                         // first round whose counts were read back
+    for (int round = 0;; round++) {
+      pa.list = ch->d_list[cur]; pa.count = cnt_list(ch->d_count, cur); pa.count_zero = cnt_list(ch->d_count, cur ^ 1);
+      pa.pend_counts = cnt_list(ch->d_count, cur); pa.pend_stripes = cnt_stripes(ch->d_count, cur);
+      pa.pend_stripes_zero = cnt_stripes(ch->d_count, cur ^ 1);
+      if (c->o.IMPLICIT) {
+        // the Newton iteration for every listed HRU; those it fails for go on the fall-back list, which the explicit kernel
+        // (the same one, on that list) solves right after (func_surf_energy_bal.c:192-222)
+        HIPCHK(ch, hipMemsetAsync(ch->d_fb_count, 0, sizeof(int) * (NBUCKET + 1), st));      // the fall-back segments and the work-list cursor
+        // persistent waves, a few per SIMD: a lane takes the next solve when its own ends (vic_implicit.hpp)
+        const int nblk = std::min(std::max((nmax + 63) / 64, 1), 4096);
+        hipLaunchKernelGGL(vic_profile_solve_implicit, dim3(nblk), dim3(64), 0, st, pa, ia);
+        HIPCHK(ch, hipGetLastError());
+        pa.list = ch->d_fb_list; pa.count = ch->d_fb_count;
+      }
+      HIPCHK(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
+      ea.list_next = ch->d_list[cur ^ 1]; ea.count_next = cnt_list(ch->d_count, cur ^ 1);
+      ea.pend_list_next = ch->d_plist[cur ^ 1]; ea.pend_count_next = cnt_stripes(ch->d_count, cur ^ 1);
+      ea.pend_list_cur = ch->d_plist[cur];
+      ea.list_thr = round > 0 ? list_thr : -1;      // the stage kernel before round 0 fills the keyed list only
+      // the device switches to the list by itself; once the host knows (RB_LAG rounds late) that it has, the grid shrinks too
+      const bool sparse = npend >= 0 && npend <= ea.list_thr;
+      hipLaunchKernelGGL(vic_surf_eval, dim3(sparse ? ((npend + 63) / 64 > 0 ? (npend + 63) / 64 : 1) : ea.map.nblocks(ch->gcount)), dim3(64), 0, st, ea);
+      HIPCHK(ch, hipGetLastError());
+      cur ^= 1;
+      ch->rounds++;
+      if (trace_rounds) {       // tuning: what every round leaves pending (a host round trip per round)
+        int n = 0, np = 0;
+        if (fd_read_count(ch, cur, &n, &np) != VICGPU_OK) return VICGPU_ERR_HIP;
+        fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->dom.chunks[0]), p, round, n, np - n, ch->gcount);
+      }
+      // The list sizes of this round travel to the host behind the kernels just launched; the host looks at the copy issued
+      // RB_LAG rounds ago, which has long arrived, so waiting for it never leaves the GPU idle.  The counts only shrink from
+      // round to round (an HRU either goes on or is through), so a stale count is a valid upper bound for the grid.
+      if (round + 2 >= FREE_ROUNDS) {
+        const int slot = round % RB_DEPTH;
+        if (rb_first < 0) rb_first = round;
+        HIPCHK(ch, hipMemcpyAsync(ch->h_count + slot * CNT_TOTAL, ch->d_count, sizeof(int) * CNT_TOTAL, hipMemcpyDeviceToHost, st));
+        HIPCHK(ch, hipEventRecord(ch->readback[slot], st));
+        rb_list[slot] = cur;
+      }
+      if (rb_first >= 0 && round - RB_LAG >= rb_first) {
+        const int slot = (round - RB_LAG) % RB_DEPTH;
+        HIPCHK(ch, hipEventSynchronize(ch->readback[slot]));
+        const int* h = ch->h_count + slot * CNT_TOTAL;
+        int n = 0;
+        for (int b = 0; b < NBUCKET; b++) n += h[rb_list[slot] * CNT_LIST_STRIDE + b];
+        const int np = cnt_pending(h, rb_list[slot]);      // solves + final evaluations on record
+        if (np == 0) break;
+        nmax = n;
+        npend = np;
+      }
+    }
+    ka.phase = p; ka.list = ch->d_list[cur]; ka.count = cnt_list(ch->d_count, cur);
+    HIPCHK(ch, NODE_DISPATCH(Nn, launch_fd_stage, ka, c->o.NF > 1, st));
+    if (p < nsub) {
+      int n = 0, ne = 0;
+      const int r = fd_read_count(ch, cur, &n, &ne);
+      if (r != VICGPU_OK) return r;
+      if (n == 0) break;
+    }
+  }
+  ch->steps++;
+  return VICGPU_OK;
+}
+
+// put_data for cells [c0, c0 + ccount) after step s of the forcing chunk (s < 0: the initialisation call)
+static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, int ccount, int s) {
+  OArgs a;
+  a.o = c->o; a.lay = c->dom.out_lay; a.ncell = c->dom.ncell; a.nhru = c->dom.nhru; a.c0 = c0; a.ccount = ccount;
+  a.rec = s < 0 ? -1 : 0; a.out_step_ratio = c->out_step_ratio;
+  a.cell_off = c->dom.d_cell_off; a.cell_list = c->dom.d_cell_list; a.cell_params = c->dom.d_cp; a.veglib = c->d_veglib;
+  a.hpi = c->dom.d_hpi; a.hpd = c->dom.d_hpd; a.sd = c->dom.d_sd; a.si = c->dom.d_si; a.flux = c->dom.d_flux;
+  a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->dom.ncell;
+  a.cell_out = c->dom.d_cell_out; a.out_data = c->dom.d_out_data; a.out_agg = c->dom.d_out_agg; a.pb = c->dom.d_pb;
+  const unsigned nblk = (unsigned)((ccount + 63) / 64);
+  // zero_output_list: the columns of these cells in every row
+  hipLaunchKernelGGL(vic_put_zero, dim3(nblk, (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
+  if (c->o.Nnode > VIC_MID_NODES) hipLaunchKernelGGL(vic_put_sum_deep, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL(vic_put_sum, dim3(nblk, PUT_NPART), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(vic_put_finish, dim3(nblk), dim3(64), 0, st, a);
+  if (s >= 0)
+    hipLaunchKernelGGL(vic_put_aggregate, dim3(nblk, (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a, c->dom.d_rowagg);
+  return hipGetLastError();
+}
+
+struct StepPlan {
+  vicgpu_ctx* c;
+  KArgs ka;
+  CArgs ca;
+  int step0, nsteps;
+};
+
+static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
+  const size_t nsub = c->o.NR + 1;
+  ka.forcing = c->d_forcing + (size_t)s * VIC_NFORCE * nsub * c->dom.ncell;
+  ka.snowflag = c->d_snowflag + (size_t)s * nsub * c->dom.ncell;
+  const int* d = &c->dmy[(size_t)s * VIC_NDMY];
+  ka.dmy.month = d[VIC_DMY_MONTH]; ka.dmy.day_in_year = d[VIC_DMY_DAY_IN_YEAR]; ka.dmy.hour = d[VIC_DMY_HOUR];
+  ka.dmy.day = d[VIC_DMY_DAY]; ka.dmy.year = d[VIC_DMY_YEAR];
+}
+
+// all steps of one vicgpu_step call for one chunk
+static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
+  vicgpu_ctx* c = plan.c;
+  HIPCHK(ch, hipSetDevice(c->device));
+  KArgs ka = plan.ka;
+  CArgs ca = plan.ca;
+  ka.glist = ch->d_glist; ka.gcount = ch->gcount; ka.map = ch->map;
+  ca.c0 = ch->c0; ca.ccount = ch->ccount;
+  const bool trace = getenv("VICGPU_TRACE") != nullptr;      // tuning: per-step wall time and Brent rounds (adds a sync per step)
+  for (int s = plan.step0; s < plan.step0 + plan.nsteps; s++) {
+    set_step_inputs(c, ka, s);
+    const long long r0 = ch->rounds;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int r = fd_step(c, ch, ka);
+    if (r != VICGPU_OK) return r;
+    if (trace) {
+      HIPCHK(ch, hipStreamSynchronize(ch->stream));
+      fprintf(stderr, "[vicgpu] step %d hour %d: %.2f ms, %lld rounds\n", s, ka.dmy.hour,
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), ch->rounds - r0);
+    }
+    hipLaunchKernelGGL(vic_cell_reduce, dim3((ch->ccount + 255) / 256), dim3(256), 0, ch->stream, ca);
+    HIPCHK(ch, hipGetLastError());
+    if (c->dom.put_on) HIPCHK(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
+  }
+  HIPCHK(ch, hipEventRecord(ch->done, ch->stream));
+  return VICGPU_OK;
+}

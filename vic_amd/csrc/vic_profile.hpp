@@ -46,6 +46,25 @@ static_assert(NBUCKET <= 64, "one lane per work-list segment when the pending to
 // Each stripe's fill counter sits on its own 128-byte line (PEND_CNT_STRIDE ints apart).
 constexpr int PEND_STRIPES = 64, PEND_CNT_STRIDE = 32;
 
+// wave-aggregated append of this lane's HRU to segment `key` of a work list (order is irrelevant: HRUs never interact).
+// One atomic per distinct key, all of them in flight together: every lane finds the lanes that share its key (one
+// ballot per possible key), the first of each group reserves the group's entries.
+VIC_DEV void list_append(int* __restrict__ list, int* count, int cap, bool pred, int key, int g) {
+  if (__ballot(pred) == 0) return;
+  unsigned long long mine = 0;
+#pragma unroll 1
+  for (int k = 0; k < NBUCKET; k++) {
+    const unsigned long long m = __ballot(pred && key == k);
+    if (key == k) mine = m;
+  }
+  const int lane = (int)__lane_id();
+  const int rank = __popcll(mine & ((1ull << lane) - 1ull));
+  int base = 0;
+  if (pred && rank == 0) base = atomicAdd(count + key, __popcll(mine));
+  base = __shfl(base, pred ? __ffsll((long long)mine) - 1 : lane);
+  if (pred) list[(size_t)key * cap + base + rank] = g;
+}
+
 struct PArgs {
   const double* __restrict__ pin;    // item blocks [nhru][Nn][PREC]
   const double* __restrict__ ts;     // trial surface temperature [nhru]
