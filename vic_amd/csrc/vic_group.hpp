@@ -1,7 +1,8 @@
 // vic_group.hpp — the device group of include/vicgpu_group.h: N shard contexts of one domain, stepped at the same time.
 //
-// Host code only: it builds on the single-context entries of include/vicgpu.h and on their pitched variants declared below,
-// which copy one shard's columns straight between the device and the caller's global [..][ncell] table.  No kernel lives here.
+// Host code only: it builds on the single-context entries of include/vicgpu.h, on their pitched variants declared below and
+// on d2h_cols (vic_pipeline.hpp), which copy one shard's columns straight between the device and the caller's global
+// [..][ncell] table, and on the checks of vic_checks.hpp, which it makes on the whole domain.  No kernel lives here.
 #pragma once
 #include <condition_variable>
 #include <functional>
@@ -10,14 +11,14 @@
 #include <thread>
 #include <vector>
 #include "vicgpu_group.h"
+#include "vic_checks.hpp"
 #include "vic_pipeline.hpp"
 
-// static helpers of vicgpu_api.hip (ld: cells per row of the caller's table)
+// static helpers of vicgpu_api.hip with a pitch (ld: cells per row of the caller's table)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
                          const int* dmy, double min_wind, int plapse, int ld);
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
-static int d2h_cols(vicgpu_ctx* c, void* dst, int ld, const void* src, size_t elem, int nrow);
 
 // One persistent host thread per shard.  run(fn) calls fn(k) on thread k for every shard and returns when all have returned.
 // Each thread selects its shard's device once at start (every library entry selects it again anyway).
@@ -211,18 +212,13 @@ int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* 
   if (!g) return VICGPU_ERR_ARG;
   g->domain_ready = false;
   if (ncell <= 0 || nhru <= 0 || !cp || !hpi || !hpd || !off || !list) return group_fail(g, VICGPU_ERR_ARG, "set_domain: bad arguments");
-  // the checks of vicgpu_set_domain on the whole domain: every index used below to slice it is valid after them
-  if (off[0] != 0 || off[ncell] != nhru) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset does not span the HRUs");
-  std::vector<char> seen(nhru, 0);
-  for (int i = 0; i < ncell; i++) {
-    if (off[i + 1] < off[i]) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset decreases");
-    for (int j = off[i]; j < off[i + 1]; j++) {
-      const int h = list[j];
-      if (h < 0 || h >= nhru || seen[h] || hpi[(size_t)HPI_CELL * nhru + h] != i)
-        return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_list entry " + std::to_string(j) + " does not match the domain");
-      seen[h] = 1;
-    }
-  }
+  // the list check on the whole domain: every index used below to slice it is valid after it (bands and vegetation indices
+  // are left to the shards' vicgpu_set_domain)
+  const DomainFault f = check_domain_lists(ncell, nhru, off, list, hpi);
+  if (f.rule == DOMAIN_OFFSET_SPAN) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset does not span the HRUs");
+  if (f.rule == DOMAIN_OFFSET_DECREASES) return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_offset decreases");
+  if (f.rule != DOMAIN_OK)
+    return group_fail(g, VICGPU_ERR_ARG, "set_domain: cell_hru_list entry " + std::to_string(f.index) + " does not match the domain");
   const int ns = g->nshard();
   std::vector<int> b(ns + 1);
   if (vicgpu_group_partition(ncell, off, ns, b.data()) != VICGPU_OK)
@@ -378,14 +374,14 @@ int vicgpu_group_get_balance(vicgpu_group* g, double* pb) {
   return group_each(g, [&](int k) {
     vicgpu_ctx* c = g->ctx[k];
     if (!c->dom.put_on) return (int)VICGPU_ERR_STATE;
-    return d2h_cols(c, pb + g->c0(k), g->ncell, c->dom.d_pb, sizeof(double), PB_NROW);
+    return d2h_cols(c, pb + g->c0(k), g->ncell, c->dom.d_pb, PB_NROW);
   });
 }
 
 int vicgpu_group_get_cell_errors(vicgpu_group* g, int* flags) {
   if (!g || !flags) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
-  return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->dom.d_cell_err, sizeof(int), 1); });
+  return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->dom.d_cell_err, 1); });
 }
 
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset) {
@@ -407,10 +403,10 @@ int vicgpu_group_set_state_records(vicgpu_group* g, const double* rec) {
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   // every record of every shard first: a reader that throws changes nothing (vicgpu_set_state_records)
   const size_t L = VICGPU_SR_LEN(g->opt.Nnode);
-  for (int j = 0; j < g->nhru; j++)
-    if ((int)rec[j * L + SR_BAND_INDEX] != g->rec_band[j] || (int)rec[j * L + SR_VEG_CLASS] != g->rec_veg[j])
-      return group_fail(g, VICGPU_ERR_ARG, "state record " + std::to_string(j) +
-                                               ": band / vegetation class do not match the domain (write_model_state.c:179-188)");
+  for (int j = 0; j < g->nhru; j++) {
+    const std::string bad = check_state_record(rec + j * L, j, g->rec_band[j], g->rec_veg[j]);
+    if (!bad.empty()) return group_fail(g, VICGPU_ERR_ARG, bad);
+  }
   return group_each(g, [&](int k) { return vicgpu_set_state_records(g->ctx[k], rec + (size_t)g->rec_first[k] * L); });
 }
 

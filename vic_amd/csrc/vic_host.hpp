@@ -2,10 +2,21 @@
 // Move-only handles: each releases what it holds in its destructor, so an entry point that returns early and a context that
 // is deleted half-built leave nothing behind.  Creation returns the runtime's error code; nothing throws.  The buffers
 // convert to the raw pointer, so the kernel-argument structs and the runtime calls take them as they took the pointers.
+// A buffer knows its element count, and its transfers (upload, download, fill, download_cols) are counted in elements and
+// checked against it: a table is sized once, where it is allocated, and a move past its end is refused, not made.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <utility>
+
+// Host <-> device copies of the set-up and read-back calls go through the context's own (non-blocking) stream and are waited
+// for there: a copy on the null stream is not ordered against kernels on a non-blocking stream, and a pageable host-to-device
+// copy may return before its last bytes have landed in device memory.
+static inline hipError_t copy_on(hipStream_t st, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
 
 // n elements of device memory (DevBuf) or of pinned host memory (PinnedBuf)
 template <typename T, bool PINNED>
@@ -27,6 +38,35 @@ struct Buf {
   T* get() const { return p; }
   operator T*() const { return p; }
   size_t size() const { return n; }
+  bool holds(size_t first, size_t count) const { return first <= n && count <= n - first; }
+  // Elements [first, first + count), or the whole buffer, on a stream; hipErrorInvalidValue, and nothing moved, past size().
+  // The copies wait for the stream (copy_on).  A fill involves no host memory and is only queued: the caller waits once.
+  hipError_t upload(hipStream_t st, const T* src, size_t first, size_t count) {
+    return holds(first, count) ? copy_on(st, p + first, src, sizeof(T) * count, hipMemcpyHostToDevice) : hipErrorInvalidValue;
+  }
+  hipError_t upload(hipStream_t st, const T* src) { return upload(st, src, 0, n); }
+  hipError_t download(hipStream_t st, T* dst, size_t first, size_t count) const {
+    return holds(first, count) ? copy_on(st, dst, p + first, sizeof(T) * count, hipMemcpyDeviceToHost) : hipErrorInvalidValue;
+  }
+  hipError_t download(hipStream_t st, T* dst) const { return download(st, dst, 0, n); }
+  hipError_t fill(hipStream_t st, int byte, size_t first, size_t count) {
+    return holds(first, count) ? hipMemsetAsync(p + first, byte, sizeof(T) * count, st) : hipErrorInvalidValue;
+  }
+  hipError_t fill(hipStream_t st, int byte) { return fill(st, byte, 0, n); }
+  hipError_t alloc_fill(size_t count, int byte, hipStream_t st) {                         // empty when either step fails
+    hipError_t e = alloc(count);
+    if (e == hipSuccess && (e = fill(st, byte)) != hipSuccess) reset();
+    return e;
+  }
+  // The table [nrow][ncell] at the start of the buffer -> the columns [0, ncell) of a host table whose rows are ld cells wide
+  // (a group reads one shard's columns straight into the caller's global table); packed when ld == ncell.  Waits like a copy.
+  hipError_t download_cols(hipStream_t st, T* dst, size_t ld, size_t nrow, size_t ncell) const {
+    if (ld < ncell || !holds(0, nrow * ncell)) return hipErrorInvalidValue;
+    if (ld == ncell) return download(st, dst, 0, nrow * ncell);
+    hipError_t e = hipMemcpy2DAsync(dst, sizeof(T) * ld, p, sizeof(T) * ncell, sizeof(T) * ncell, nrow, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+  }
   T* p = nullptr;
   size_t n = 0;
 };

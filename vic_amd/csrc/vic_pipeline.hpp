@@ -1,10 +1,12 @@
-// vic_pipeline.hpp — the host pipeline: the context (vicgpu_ctx), what lives as long as a domain (Domain, FdChunk), the
-// kernel-argument structs filled from them, the launchers, and the step of the finite-difference pipeline (fd_step: the
-// round loop; fd_chunk_run: all steps of one vicgpu_step call for one cell chunk).  Host code only, no kernels.
+// vic_pipeline.hpp — the host pipeline: the context (vicgpu_ctx), its tuning variables (Tuning), what lives as long as a
+// domain (Domain, FdChunk) and the steps of vicgpu_set_domain that fill it, the kernel-argument structs filled from them,
+// the launchers, and the step of the finite-difference pipeline (fd_step: the round loop; fd_chunk_run: all steps of one
+// vicgpu_step call for one cell chunk).  Host code only, no kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -30,20 +32,6 @@ using namespace vic;
       return VICGPU_ERR_HIP;                                                                           \
     }                                                                                                  \
   } while (0)
-
-// Host <-> device copies and fills of the set-up and read-back calls go through the context's own (non-blocking) stream
-// and are waited for there: a copy on the null stream is not ordered against kernels on a non-blocking stream, and a
-// pageable host-to-device copy may return before its last bytes have landed in device memory.
-static hipError_t copy_on(hipStream_t st, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  return e;
-}
-static hipError_t fill_on(hipStream_t st, void* dst, int value, size_t bytes) {
-  hipError_t e = hipMemsetAsync(dst, value, bytes, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  return e;
-}
 
 // ------------------------------------------------------------------------------------------------ context
 // A chunk of cells with all their HRUs.  Cells never interact, so every chunk runs the whole step sequence on its own
@@ -94,11 +82,57 @@ struct Domain {
   DevBuf<unsigned char> d_rowagg;  // [out_nrow] aggregation type of every output row
 };
 
+// The tuning variables of the environment: overrides for A/B runs, profiles and traces, not API (table in DESIGN.md (d)).
+// Read once per vicgpu_set_domain, so a domain runs on what the environment said when it was set, and a second
+// vicgpu_set_domain starts from the defaults again.
+struct Tuning {
+  bool node_newton = false;        // VICGPU_NODE_SOLVER = "newton": the safeguarded Newton node root finder; default options.NODE_SOLVER
+  int eval_list_pct = 75;          // VICGPU_EVAL_LIST_PCT, 0..100: sparse evaluation rounds once at most this share of the HRUs is pending; 0 = never
+  int nchunk = 1;                  // VICGPU_CHUNKS, 1..16 and at most ncell: cell chunks as independent pipelines; default 2 from 20 000 cells up
+  int profile_waves_pct = 100;     // VICGPU_PROFILE_WAVES_PCT, 5..100: a chunk's profile kernel's share of the resident wave slots; default 50 with chunks
+  bool xcd_map = true;             // VICGPU_NO_XCD_MAP (set): plain instead of XCD-aware launch order
+  bool trace_rounds = false;       // VICGPU_TRACE_ROUNDS (set): what every round leaves pending (a host round trip per round)
+  bool trace = false;              // VICGPU_TRACE (set): per-step wall time and Brent rounds (a wait per step)
+  bool stats = false;              // VICGPU_STATS (set): Brent rounds per step of every chunk, printed by vicgpu_destroy
+};
+static Tuning read_tuning(int node_solver, int ncell) {
+  Tuning t;
+  // frozen-node root finder (vic_profile.hpp): the option, overridable for A/B runs
+  t.node_newton = node_solver == VIC_NODE_SOLVER_NEWTON;
+  if (const char* ev = getenv("VICGPU_NODE_SOLVER")) t.node_newton = (strcmp(ev, "newton") == 0);
+  if (const char* ev = getenv("VICGPU_EVAL_LIST_PCT")) {
+    const int pct = atoi(ev);
+    if (pct >= 0 && pct <= 100) t.eval_list_pct = pct;
+  }
+  // Cell chunks: every kernel of the pipeline is stalled most of its time (dependent fp64 chains in the profile kernel, memory
+  // latency in the others: 15 % VALU-active per wave), so two pipelines side by side fill each other's gaps and thin tail
+  // rounds: -6 % step time at 2.5 M HRUs (27.3 vs 29.0 ms, same-box A/B); three or more lose again.  Default: two chunks for
+  // domains of 20k cells or more (VICGPU_CHUNKS=1 gives per-kernel profiles whose durations add up to the step).
+  t.nchunk = (ncell >= 20000) ? 2 : 1;
+  if (const char* ev = getenv("VICGPU_CHUNKS")) t.nchunk = atoi(ev);
+  if (t.nchunk < 1) t.nchunk = 1;
+  if (t.nchunk > 16) t.nchunk = 16;
+  if (t.nchunk > ncell) t.nchunk = ncell;
+  // A chunk's profile kernel takes half of the resident wave slots when chunks run side by side, so that the other chunk's
+  // kernels find free SIMD slots beside it (26.5 vs 26.9 ms per step with two chunks, same box, both repetitions)
+  t.profile_waves_pct = t.nchunk > 1 ? 50 : 100;
+  if (const char* ev = getenv("VICGPU_PROFILE_WAVES_PCT")) {
+    const int pct = atoi(ev);
+    if (pct >= 5 && pct <= 100) t.profile_waves_pct = pct;
+  }
+  t.xcd_map = getenv("VICGPU_NO_XCD_MAP") == nullptr;
+  t.trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
+  t.trace = getenv("VICGPU_TRACE") != nullptr;
+  t.stats = getenv("VICGPU_STATS") != nullptr;
+  return t;
+}
+
 struct vicgpu_ctx {
   vicgpu_options opt;
   Opt o;
   int device;
   std::string err;
+  Tuning tune;
   int nveg_rows = 0;
   DevBuf<double> d_veglib;
   Domain dom;
@@ -126,8 +160,6 @@ struct vicgpu_ctx {
   int write_fluxes = 1;
   int steps_done = 0;
   int profile_waves = 0;           // resident waves of the profile kernel
-  int eval_list_pct = 75;          // sparse evaluation rounds (lane = pending HRU) once at most this percentage of the HRUs is pending
-  bool node_newton = false;        // frozen-node root finder: safeguarded Newton instead of the reference's Brent iteration
   int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
   int out_step_ratio = 1;
 };
@@ -284,8 +316,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
   PArgs pa = profile_args(c, ch);
   EArgs ea = eval_args(c, ch, ka);
   const IArgs ia = c->o.IMPLICIT ? implicit_args(c, ch) : IArgs{};      // the fall-back lists exist with IMPLICIT only
-  const int list_thr = (int)((long long)ch->gcount * c->eval_list_pct / 100);
-  const bool trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
+  const int list_thr = (int)((long long)ch->gcount * c->tune.eval_list_pct / 100);
   const int FREE_ROUNDS = 6;       // a Brent solve needs two bracket evaluations, a few iterations and the final evaluation
   const int nsub = c->o.NF;
   for (int p = 1; p <= nsub; p++) {
@@ -307,7 +338,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
         HIPCHK(ch, hipGetLastError());
         pa.list = ch->d_fb_list; pa.count = ch->d_fb_count;
       }
-      HIPCHK(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->node_newton, st));
+      HIPCHK(ch, NODE_DISPATCH(Nn, launch_profile, pa, nmax, c->profile_waves, c->tune.node_newton, st));
       ea.list_next = ch->d_list[cur ^ 1]; ea.count_next = cnt_list(ch->d_count, cur ^ 1);
       ea.pend_list_next = ch->d_plist[cur ^ 1]; ea.pend_count_next = cnt_stripes(ch->d_count, cur ^ 1);
       ea.pend_list_cur = ch->d_plist[cur];
@@ -318,7 +349,7 @@ static int fd_step(vicgpu_ctx* c, FdChunk* ch, KArgs ka) {
       HIPCHK(ch, hipGetLastError());
       cur ^= 1;
       ch->rounds++;
-      if (trace_rounds) {       // tuning: what every round leaves pending (a host round trip per round)
+      if (c->tune.trace_rounds) {       // tuning: what every round leaves pending (a host round trip per round)
         int n = 0, np = 0;
         if (fd_read_count(ch, cur, &n, &np) != VICGPU_OK) return VICGPU_ERR_HIP;
         fprintf(stderr, "vicgpu rounds: chunk %d sub-step %d round %d leaves %d solves + %d evaluation-only of %d\n", (int)(ch - &c->dom.chunks[0]), p, round, n, np - n, ch->gcount);
@@ -402,14 +433,13 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
   CArgs ca = plan.ca;
   ka.glist = ch->d_glist; ka.gcount = ch->gcount; ka.map = ch->map;
   ca.c0 = ch->c0; ca.ccount = ch->ccount;
-  const bool trace = getenv("VICGPU_TRACE") != nullptr;      // tuning: per-step wall time and Brent rounds (adds a sync per step)
   for (int s = plan.step0; s < plan.step0 + plan.nsteps; s++) {
     set_step_inputs(c, ka, s);
     const long long r0 = ch->rounds;
     const auto t0 = std::chrono::steady_clock::now();
     const int r = fd_step(c, ch, ka);
     if (r != VICGPU_OK) return r;
-    if (trace) {
+    if (c->tune.trace) {      // tuning: per-step wall time and Brent rounds
       HIPCHK(ch, hipStreamSynchronize(ch->stream));
       fprintf(stderr, "[vicgpu] step %d hour %d: %.2f ms, %lld rounds\n", s, ka.dmy.hour,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), ch->rounds - r0);
@@ -419,5 +449,136 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
     if (c->dom.put_on) HIPCHK(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
   }
   HIPCHK(ch, hipEventRecord(ch->done, ch->stream));
+  return VICGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ vicgpu_set_domain, step by step
+// The three steps after the argument check, on a context whose Domain is fresh and has its sizes.  Each table's shape is
+// named once, where it is allocated; what starts as zero is filled on the context's stream without a wait of its own
+// (vicgpu_set_domain waits once, before it returns or drops a half-built domain).
+
+// the tables of the domain and of the model state
+static int domain_tables(vicgpu_ctx* c, const double* cell_params, const int* hpi, const double* hpd, const int* cell_hru_offset,
+                         const int* cell_hru_list) {
+  Domain& d = c->dom;
+  hipStream_t st = c->stream;
+  const size_t ncell = d.ncell, nhru = d.nhru;
+  const int Nn = c->opt.Nnode, Nb = c->opt.Nband;
+  for (size_t g = 0; g < nhru; g++) if (hpi[HPI_IS_GLACIER * nhru + g]) d.any_glacier = true;
+  HIPCHK(c, d.d_cp.alloc(VIC_CPX_NROW(Nn, Nb) * ncell));                       // the caller's rows + the derived rows
+  HIPCHK(c, d.d_cp.upload(st, cell_params, 0, VICGPU_CP_NROW(Nn, Nb) * ncell));
+  hipLaunchKernelGGL(vic_derive_cell_params, dim3((c->dom.ncell + 255) / 256), dim3(256), 0, st, c->dom.d_cp, c->dom.ncell, Nn, Nb);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, d.d_hpi.alloc(HPI_NROW * nhru));
+  HIPCHK(c, d.d_hpi.upload(st, hpi));
+  HIPCHK(c, d.d_hpd.alloc(HPD_NROW * nhru));
+  HIPCHK(c, d.d_hpd.upload(st, hpd));
+  HIPCHK(c, d.d_cell_off.alloc(ncell + 1));
+  HIPCHK(c, d.d_cell_off.upload(st, cell_hru_offset));
+  HIPCHK(c, d.d_cell_list.alloc(nhru));
+  HIPCHK(c, d.d_cell_list.upload(st, cell_hru_list));
+  HIPCHK(c, d.d_sd.alloc_fill(VICGPU_SD_NROW(Nn) * nhru, 0, st));
+  HIPCHK(c, d.d_si.alloc_fill(VICGPU_SI_NROW(Nn) * nhru, 0, st));
+  HIPCHK(c, d.d_flux.alloc_fill(FX_NROW * nhru, 0, st));
+  HIPCHK(c, d.d_cell_out.alloc_fill(CO_NROW * ncell, 0, st));
+  HIPCHK(c, d.d_accum.alloc_fill(CA_NROW * ncell, 0, st));
+  HIPCHK(c, d.d_hru_err.alloc_fill(nhru, 0, st));
+  HIPCHK(c, d.d_cell_err.alloc_fill(ncell, 0, st));
+  return VICGPU_OK;
+}
+
+// the workspace of the finite-difference pipeline (QUICK_FLUX off)
+static int domain_fd_workspace(vicgpu_ctx* c) {
+  Domain& d = c->dom;
+  hipStream_t st = c->stream;
+  const size_t nhru = d.nhru;
+  const int Nn = c->o.Nnode;
+  const size_t words = NODE_DISPATCH(Nn, ctx_words);
+  HIPCHK(c, d.d_ctx.alloc(ctx_padded_words(words) * ((nhru + 63) / 64 * 64)));
+  HIPCHK(c, d.d_ts.alloc(nhru));
+  HIPCHK(c, d.d_pin.alloc_fill((size_t)Nn * PREC * nhru, 0, st));
+  HIPCHK(c, d.d_pout.alloc_fill((size_t)pout_hru_stride(Nn) * nhru, 0, st));
+  HIPCHK(c, d.d_pslot.alloc_fill(nhru, 0, st));
+  HIPCHK(c, d.d_hkey.alloc_fill(nhru, 0, st));
+  HIPCHK(c, d.d_hstate.alloc_fill(nhru, 0, st));
+  if (c->o.QUICK_SOLVE) HIPCHK(c, d.d_jl.alloc_fill(nhru, 0, st));
+  if (c->o.IMPLICIT) {
+    HIPCHK(c, d.d_pimp.alloc_fill((size_t)Nn * PIMP * nhru, 0, st));
+    HIPCHK(c, d.d_lastexp.alloc_fill(nhru, 0xFF, st));
+  }
+  return VICGPU_OK;
+}
+
+// the cell chunks (Tuning::nchunk): independent pipelines on their own streams and host threads
+static int domain_chunks(vicgpu_ctx* c, const int* hpi, const int* cell_hru_offset, const int* cell_hru_list) {
+  Domain& d = c->dom;
+  const int ncell = d.ncell, nhru = d.nhru, nchunk = c->tune.nchunk;
+  const int waves = NODE_DISPATCH(c->o.Nnode, profile_resident_waves, c->device, c->tune.node_newton);
+  c->profile_waves = std::max(waves * c->tune.profile_waves_pct / 100, 1);
+  d.chunks.resize(nchunk);
+  for (int k = 0; k < nchunk; k++) {
+    FdChunk& ch = d.chunks[k];
+    ch.c0 = (int)((long long)ncell * k / nchunk);
+    ch.ccount = (int)((long long)ncell * (k + 1) / nchunk) - ch.c0;
+    std::vector<int> gl(cell_hru_list + cell_hru_offset[ch.c0], cell_hru_list + cell_hru_offset[ch.c0 + ch.ccount]);
+    std::sort(gl.begin(), gl.end());
+    ch.gcount = (int)gl.size();
+    ch.map = LaunchMap();
+    if (ch.ccount > 0 && ch.gcount % ch.ccount == 0 && c->tune.xcd_map) {
+      const int nslot = ch.gcount / ch.ccount;
+      bool regular = true;
+      for (int sl = 0; sl < nslot && regular; sl++)
+        for (int i = 0; i < ch.ccount; i++)
+          if (gl[(size_t)sl * ch.ccount + i] != sl * ncell + ch.c0 + i || hpi[(size_t)HPI_CELL * nhru + gl[(size_t)sl * ch.ccount + i]] != ch.c0 + i) {
+            regular = false;
+            break;
+          }
+      if (regular) { ch.map.nslot = nslot; ch.map.ccount = ch.ccount; }
+    }
+    const size_t gn = ch.gcount > 0 ? ch.gcount : 1;
+    ch.list_cap = (int)gn;
+    HIPCHK(c, ch.d_glist.alloc(gn));
+    if (ch.gcount) HIPCHK(c, ch.d_glist.upload(c->stream, gl.data()));
+    HIPCHK(c, ch.d_list[0].alloc(gn * NBUCKET));
+    HIPCHK(c, ch.d_list[1].alloc(gn * NBUCKET));
+    HIPCHK(c, ch.d_count.alloc(CNT_TOTAL));
+    // a wave appends at most 64 entries to stripe blockIdx.x % PEND_STRIPES, and no evaluation grid is larger than the dense one
+    ch.pend_cap = 64 * ((ch.map.nblocks(ch.gcount) + PEND_STRIPES - 1) / PEND_STRIPES);
+    if (ch.pend_cap < 64) ch.pend_cap = 64;
+    HIPCHK(c, ch.d_plist[0].alloc((size_t)ch.pend_cap * PEND_STRIPES));
+    HIPCHK(c, ch.d_plist[1].alloc((size_t)ch.pend_cap * PEND_STRIPES));
+    if (c->o.IMPLICIT) {
+      HIPCHK(c, ch.d_fb_list.alloc(gn * NBUCKET));
+      HIPCHK(c, ch.d_fb_count.alloc(NBUCKET + 1));
+    }
+    HIPCHK(c, ch.h_count.alloc((size_t)CNT_TOTAL * RB_DEPTH));
+    HIPCHK(c, ch.stream.create());
+    HIPCHK(c, ch.done.create(hipEventDisableTiming));
+    for (Event& e : ch.readback) HIPCHK(c, e.create(hipEventDisableTiming));
+  }
+  return VICGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ read-backs
+// `count` elements from the start of a device table to the host (all of it when count is left out), after everything
+// queued on the context's stream
+template <typename T>
+static int d2h(vicgpu_ctx* c, T* dst, const DevBuf<T>& src, size_t count) {
+  if (!c || !dst || !src) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, src.download(c->stream, dst, 0, count));
+  return VICGPU_OK;
+}
+template <typename T>
+static int d2h(vicgpu_ctx* c, T* dst, const DevBuf<T>& src) { return d2h(c, dst, src, src.size()); }
+
+// the same for the first nrow rows of a per-cell table into the columns [0, ncell) of a host table whose rows are ld cells wide
+template <typename T>
+static int d2h_cols(vicgpu_ctx* c, T* dst, int ld, const DevBuf<T>& src, int nrow) {
+  if (!c || !dst || !src || ld < c->dom.ncell) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, src.download_cols(c->stream, dst, ld, nrow, c->dom.ncell));
   return VICGPU_OK;
 }

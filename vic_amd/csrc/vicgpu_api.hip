@@ -7,9 +7,12 @@
 //   vic_hru_io.hpp       KArgs, LaunchMap and the HRU table I/O
 //   vic_kernels.hpp      vic_hru_step, vic_fd_stage, vic_surf_eval
 //   vic_aux_kernels.hpp  glacier fit, derived cell rows, test hooks, vic_cell_reduce, state records, forcing derivation
-//   vic_host.hpp         owners of every device buffer, pinned block, stream and event
-//   vic_pipeline.hpp     vicgpu_ctx, Domain, FdChunk, the launchers and fd_step
+//   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
+//   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
+//   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
 //   vic_group.hpp        the device group (include/vicgpu_group.h): host code on top of the entries below
+// An entry moves a table that a DevBuf owns through that buffer (upload / download / fill, counted in elements and checked
+// against its size); sizeof is left for what no DevBuf owns.
 // The order of the device headers below is the order of the device code in the code object (calls to the out-of-line
 // calc_blowing_snow are pc-relative): keep it.
 #include <hip/hip_runtime.h>
@@ -26,6 +29,7 @@
 #include "vic_profile.hpp"
 #include "vic_putdata.hpp"
 #include "vic_host.hpp"
+#include "vic_checks.hpp"
 #include "vic_implicit.hpp"
 #include "vic_ctx.hpp"
 #include "vic_hru_io.hpp"
@@ -105,7 +109,7 @@ void vicgpu_destroy(vicgpu_ctx* c) {
   HIPIGN(hipSetDevice(c->device));
   if (c->stream) HIPIGN(hipStreamSynchronize(c->stream));
   if (c->copy_stream) HIPIGN(hipStreamSynchronize(c->copy_stream));
-  if (getenv("VICGPU_STATS"))
+  if (c->tune.stats)
     for (size_t k = 0; k < c->dom.chunks.size(); k++)
       if (c->dom.chunks[k].steps)
         fprintf(stderr, "[vicgpu] chunk %zu: %d cells, %d HRUs, %lld steps, %.1f Brent rounds per step\n", k, c->dom.chunks[k].ccount,
@@ -117,7 +121,7 @@ int vicgpu_set_veglib(vicgpu_ctx* c, int nrow, const double* veglib) {
   if (!c || !veglib || nrow != c->opt.nveg_types + 4) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, c->d_veglib.alloc((size_t)nrow * VL_NFIELD));
-  HIPCHK(c, copy_on(c->stream, c->d_veglib, veglib, sizeof(double) * nrow * VL_NFIELD, hipMemcpyHostToDevice));
+  HIPCHK(c, c->d_veglib.upload(c->stream, veglib));
   c->nveg_rows = nrow;
   return VICGPU_OK;
 }
@@ -125,154 +129,18 @@ int vicgpu_set_veglib(vicgpu_ctx* c, int nrow, const double* veglib) {
 static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cell_params, const int* hpi, const double* hpd,
                            const int* cell_hru_offset, const int* cell_hru_list) {
   if (!c || ncell <= 0 || nhru <= 0 || !cell_params || !hpi || !hpd || !cell_hru_offset || !cell_hru_list) return VICGPU_ERR_ARG;
-  // host-side shape checks: every index the kernels dereference is validated here, once
-  if (cell_hru_offset[0] != 0 || cell_hru_offset[ncell] != nhru) return VICGPU_ERR_ARG;
-  for (int i = 0; i < ncell; i++) if (cell_hru_offset[i + 1] < cell_hru_offset[i]) return VICGPU_ERR_ARG;
-  {
-    std::vector<char> seen(nhru, 0);
-    for (int i = 0; i < ncell; i++)
-      for (int k = cell_hru_offset[i]; k < cell_hru_offset[i + 1]; k++) {
-        int g = cell_hru_list[k];
-        if (g < 0 || g >= nhru || seen[g] || hpi[(size_t)HPI_CELL * nhru + g] != i) return VICGPU_ERR_ARG;
-        seen[g] = 1;
-      }
-    for (int g = 0; g < nhru; g++) {
-      if (!seen[g]) return VICGPU_ERR_ARG;
-      int b = hpi[(size_t)HPI_BAND * nhru + g], v = hpi[(size_t)HPI_VEG_INDEX * nhru + g];
-      if (b < 0 || b >= c->opt.Nband || v < 0 || v >= c->opt.nveg_types + 4) return VICGPU_ERR_ARG;
-    }
-  }
+  if (check_domain_lists(ncell, nhru, cell_hru_offset, cell_hru_list, hpi, c->opt.Nband, c->opt.nveg_types + 4).rule != DOMAIN_OK)
+    return VICGPU_ERR_ARG;         // the domain the context holds stays as it is
   HIPCHK(c, hipSetDevice(c->device));
   free_domain(c);
+  c->tune = read_tuning(c->opt.NODE_SOLVER, ncell);
   c->dom.ncell = ncell; c->dom.nhru = nhru;
-  c->dom.any_glacier = false;
-  for (int g = 0; g < nhru; g++) if (hpi[(size_t)HPI_IS_GLACIER * nhru + g]) c->dom.any_glacier = true;
-  const size_t cp_n = (size_t)VICGPU_CP_NROW(c->opt.Nnode, c->opt.Nband) * ncell;
-  const size_t cpx_n = (size_t)VIC_CPX_NROW(c->opt.Nnode, c->opt.Nband) * ncell;      // + the derived rows
-  const size_t sd_n = (size_t)VICGPU_SD_NROW(c->opt.Nnode) * nhru, si_n = (size_t)VICGPU_SI_NROW(c->opt.Nnode) * nhru;
-  HIPCHK(c, c->dom.d_cp.alloc(cpx_n));
-  HIPCHK(c, c->dom.d_hpi.alloc((size_t)HPI_NROW * nhru));
-  HIPCHK(c, c->dom.d_hpd.alloc((size_t)HPD_NROW * nhru));
-  HIPCHK(c, c->dom.d_cell_off.alloc((size_t)ncell + 1));
-  HIPCHK(c, c->dom.d_cell_list.alloc(nhru));
-  HIPCHK(c, c->dom.d_sd.alloc(sd_n));
-  HIPCHK(c, c->dom.d_si.alloc(si_n));
-  HIPCHK(c, c->dom.d_flux.alloc((size_t)FX_NROW * nhru));
-  HIPCHK(c, c->dom.d_cell_out.alloc((size_t)CO_NROW * ncell));
-  HIPCHK(c, c->dom.d_accum.alloc((size_t)CA_NROW * ncell));
-  HIPCHK(c, c->dom.d_hru_err.alloc(nhru));
-  HIPCHK(c, c->dom.d_cell_err.alloc(ncell));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_cp, cell_params, sizeof(double) * cp_n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vic_derive_cell_params, dim3((ncell + 255) / 256), dim3(256), 0, c->stream, c->dom.d_cp, ncell, c->opt.Nnode, c->opt.Nband);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_hpi, hpi, sizeof(int) * HPI_NROW * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_hpd, hpd, sizeof(double) * HPD_NROW * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_cell_off, cell_hru_offset, sizeof(int) * (ncell + 1), hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_cell_list, cell_hru_list, sizeof(int) * nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_sd, 0, sizeof(double) * sd_n));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_si, 0, sizeof(int) * si_n));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_flux, 0, sizeof(double) * FX_NROW * nhru));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_cell_out, 0, sizeof(double) * CO_NROW * ncell));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_accum, 0, sizeof(double) * CA_NROW * ncell));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_hru_err, 0, sizeof(int) * nhru));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_cell_err, 0, sizeof(int) * ncell));
   c->dom.fd = !c->o.QUICK_FLUX;
-  if (c->dom.fd) {
-    const int Nn = c->o.Nnode;
-    const size_t words = NODE_DISPATCH(Nn, ctx_words);
-    HIPCHK(c, c->dom.d_ctx.alloc(ctx_padded_words(words) * (((size_t)nhru + 63) / 64 * 64)));
-    HIPCHK(c, c->dom.d_pin.alloc((size_t)Nn * PREC * nhru));
-    HIPCHK(c, c->dom.d_ts.alloc(nhru));
-    HIPCHK(c, c->dom.d_pout.alloc((size_t)pout_hru_stride(Nn) * nhru));
-    HIPCHK(c, c->dom.d_pslot.alloc(nhru));
-    HIPCHK(c, c->dom.d_hkey.alloc(nhru));
-    HIPCHK(c, fill_on(c->stream, c->dom.d_hkey, 0, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->dom.d_pslot, 0, sizeof(int) * nhru));
-    HIPCHK(c, c->dom.d_hstate.alloc(nhru));
-    HIPCHK(c, fill_on(c->stream, c->dom.d_hstate, 0, sizeof(int) * nhru));
-    HIPCHK(c, fill_on(c->stream, c->dom.d_pin, 0, sizeof(double) * (size_t)Nn * PREC * nhru));
-    HIPCHK(c, fill_on(c->stream, c->dom.d_pout, 0, sizeof(double) * (size_t)pout_hru_stride(Nn) * nhru));
-    if (c->o.QUICK_SOLVE) {
-      HIPCHK(c, c->dom.d_jl.alloc(nhru));
-      HIPCHK(c, fill_on(c->stream, c->dom.d_jl, 0, sizeof(int) * nhru));
-    }
-    if (c->o.IMPLICIT) {
-      HIPCHK(c, c->dom.d_pimp.alloc((size_t)Nn * PIMP * nhru));
-      HIPCHK(c, c->dom.d_lastexp.alloc(nhru));
-      HIPCHK(c, fill_on(c->stream, c->dom.d_pimp, 0, sizeof(double) * (size_t)Nn * PIMP * nhru));
-      HIPCHK(c, fill_on(c->stream, c->dom.d_lastexp, 0xFF, sizeof(int) * nhru));
-    }
-    // frozen-node root finder (vic_profile.hpp): the option, overridable for A/B runs
-    c->node_newton = c->opt.NODE_SOLVER == VIC_NODE_SOLVER_NEWTON;
-    if (const char* ev = getenv("VICGPU_NODE_SOLVER")) c->node_newton = (strcmp(ev, "newton") == 0);
-    c->profile_waves = NODE_DISPATCH(Nn, profile_resident_waves, c->device, c->node_newton);
-    // tuning: the pending share (percent of the chunk's HRUs) from which the evaluation rounds run from the pending list; 0 = never
-    if (const char* ev = getenv("VICGPU_EVAL_LIST_PCT")) {
-      const int pct = atoi(ev);
-      if (pct >= 0 && pct <= 100) c->eval_list_pct = pct;
-    }
-    // cell chunks (VICGPU_CHUNKS): independent pipelines on their own streams and host threads.  Every kernel of the pipeline
-    // is stalled most of its time (dependent fp64 chains in the profile kernel, memory latency in the others: 15 % VALU-active
-    // per wave), so two pipelines side by side fill each other's gaps and thin tail rounds: -6 % step time at 2.5 M HRUs
-    // (27.3 vs 29.0 ms, same-box A/B); three or more lose again.  Default: two chunks for domains of 20k cells or more
-    // (VICGPU_CHUNKS=1 gives per-kernel profiles whose durations add up to the step).
-    int nchunk = (ncell >= 20000) ? 2 : 1;
-    if (const char* ev = getenv("VICGPU_CHUNKS")) nchunk = atoi(ev);
-    if (nchunk < 1) nchunk = 1;
-    if (nchunk > 16) nchunk = 16;
-    if (nchunk > ncell) nchunk = ncell;
-    // A chunk's profile kernel takes half of the resident wave slots when chunks run side by side, so that the other chunk's
-    // kernels find free SIMD slots beside it (26.5 vs 26.9 ms per step with two chunks, same box, both repetitions);
-    // VICGPU_PROFILE_WAVES_PCT overrides (tuning)
-    int waves_pct = nchunk > 1 ? 50 : 100;
-    if (const char* ev = getenv("VICGPU_PROFILE_WAVES_PCT")) {
-      const int pct = atoi(ev);
-      if (pct >= 5 && pct <= 100) waves_pct = pct;
-    }
-    c->profile_waves = c->profile_waves * waves_pct / 100 > 0 ? c->profile_waves * waves_pct / 100 : 1;
-    c->dom.chunks.resize(nchunk);
-    for (int k = 0; k < nchunk; k++) {
-      FdChunk& ch = c->dom.chunks[k];
-      ch.c0 = (int)((long long)ncell * k / nchunk);
-      ch.ccount = (int)((long long)ncell * (k + 1) / nchunk) - ch.c0;
-      std::vector<int> gl(cell_hru_list + cell_hru_offset[ch.c0], cell_hru_list + cell_hru_offset[ch.c0 + ch.ccount]);
-      std::sort(gl.begin(), gl.end());
-      ch.gcount = (int)gl.size();
-      ch.map = LaunchMap();
-      if (ch.ccount > 0 && ch.gcount % ch.ccount == 0 && !getenv("VICGPU_NO_XCD_MAP")) {
-        const int nslot = ch.gcount / ch.ccount;
-        bool regular = true;
-        for (int sl = 0; sl < nslot && regular; sl++)
-          for (int i = 0; i < ch.ccount; i++)
-            if (gl[(size_t)sl * ch.ccount + i] != sl * ncell + ch.c0 + i || hpi[(size_t)HPI_CELL * nhru + gl[(size_t)sl * ch.ccount + i]] != ch.c0 + i) {
-              regular = false;
-              break;
-            }
-        if (regular) { ch.map.nslot = nslot; ch.map.ccount = ch.ccount; }
-      }
-      const size_t gn = ch.gcount > 0 ? ch.gcount : 1;
-      HIPCHK(c, ch.d_glist.alloc(gn));
-      ch.list_cap = ch.gcount > 0 ? ch.gcount : 1;
-      HIPCHK(c, ch.d_list[0].alloc(gn * NBUCKET));
-      HIPCHK(c, ch.d_list[1].alloc(gn * NBUCKET));
-      HIPCHK(c, ch.d_count.alloc(CNT_TOTAL));
-      // a wave appends at most 64 entries to stripe blockIdx.x % PEND_STRIPES, and no evaluation grid is larger than the dense one
-      ch.pend_cap = 64 * ((ch.map.nblocks(ch.gcount) + PEND_STRIPES - 1) / PEND_STRIPES);
-      if (ch.pend_cap < 64) ch.pend_cap = 64;
-      HIPCHK(c, ch.d_plist[0].alloc((size_t)ch.pend_cap * PEND_STRIPES));
-      HIPCHK(c, ch.d_plist[1].alloc((size_t)ch.pend_cap * PEND_STRIPES));
-      if (c->o.IMPLICIT) {
-        HIPCHK(c, ch.d_fb_list.alloc(gn * NBUCKET));
-        HIPCHK(c, ch.d_fb_count.alloc(NBUCKET + 1));
-      }
-      HIPCHK(c, ch.h_count.alloc((size_t)CNT_TOTAL * RB_DEPTH));
-      if (ch.gcount) HIPCHK(c, copy_on(c->stream, ch.d_glist, gl.data(), sizeof(int) * ch.gcount, hipMemcpyHostToDevice));
-      HIPCHK(c, ch.stream.create());
-      HIPCHK(c, ch.done.create(hipEventDisableTiming));
-      for (Event& e : ch.readback) HIPCHK(c, e.create(hipEventDisableTiming));
-    }
-  }
+  int r = domain_tables(c, cell_params, hpi, hpd, cell_hru_offset, cell_hru_list);
+  if (r == VICGPU_OK && c->dom.fd) r = domain_fd_workspace(c);
+  if (r == VICGPU_OK && c->dom.fd) r = domain_chunks(c, hpi, cell_hru_offset, cell_hru_list);
+  if (r != VICGPU_OK) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the one wait for every fill queued above
   return VICGPU_OK;
 }
 
@@ -283,6 +151,7 @@ int vicgpu_set_domain(vicgpu_ctx* c, int ncell, int nhru, const double* cell_par
   if (r == VICGPU_OK) c->dom.domain_ready = true;
   else if (r == VICGPU_ERR_HIP || r == VICGPU_ERR_NOMEM) {     // failed half-way: leave no partially built domain behind
     HIPIGN(hipSetDevice(c->device));
+    HIPIGN(hipStreamSynchronize(c->stream));                   // fills may still be queued on its tables
     free_domain(c);
   }
   return r;
@@ -293,8 +162,8 @@ int vicgpu_set_state(vicgpu_ctx* c, const double* sd, const int* si) {
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_sd, sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_si, si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, c->dom.d_sd.upload(c->stream, sd));
+  HIPCHK(c, c->dom.d_si.upload(c->stream, si));
   return VICGPU_OK;
 }
 
@@ -303,8 +172,8 @@ int vicgpu_get_state(vicgpu_ctx* c, double* sd, int* si) {
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, sd, c->dom.d_sd, sizeof(double) * VICGPU_SD_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyDeviceToHost));
-  HIPCHK(c, copy_on(c->stream, si, c->dom.d_si, sizeof(int) * VICGPU_SI_NROW(c->opt.Nnode) * c->dom.nhru, hipMemcpyDeviceToHost));
+  HIPCHK(c, c->dom.d_sd.download(c->stream, sd));
+  HIPCHK(c, c->dom.d_si.download(c->stream, si));
   return VICGPU_OK;
 }
 
@@ -340,22 +209,22 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
     if (m < 1 || m > 12) return VICGPU_ERR_ARG;          // month indexes the veg library tables
   }
   const size_t nsub = c->o.NR + 1;
-  const size_t fbytes = sizeof(double) * (size_t)nsteps * VIC_NFORCE * nsub * c->dom.ncell;
-  const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell;
-  const size_t rbytes = raw ? sizeof(double) * (size_t)nsteps * VIC_NRAW * c->o.dt * c->dom.ncell : 0;
+  const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell, nf = VIC_NFORCE * sbytes;      // flags (a byte each) and forcing values
+  const size_t nraw = raw ? (size_t)nsteps * VIC_NRAW * c->o.dt * c->dom.ncell : 0;
+  const size_t fbytes = sizeof(double) * nf, rbytes = sizeof(double) * nraw;                   // in the staging area
   const int t = (c->cur == 0) ? 1 : 0;
   vicgpu_ctx::ForcingSlot& sl = c->slot[t];
   // the slot's previous upload may still be reading its staging area; the steps that read the slot's device buffers were
   // queued before `released` was recorded (vicgpu_swap_forcing): the copy stream waits for that, not the host
   if (sl.upload_pending) { HIPCHK(c, hipEventSynchronize(sl.uploaded)); sl.upload_pending = false; }
   if (sl.was_current) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.released, 0));
-  const bool grow = fbytes > sizeof(double) * sl.d_f.size() || sbytes > sl.d_s.size() || rbytes > sizeof(double) * sl.d_raw.size();
+  const bool grow = nf > sl.d_f.size() || sbytes > sl.d_s.size() || nraw > sl.d_raw.size();
   if (grow) {                                            // re-allocation: nothing may still use the old buffers
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     if (sl.was_current) HIPCHK(c, hipEventSynchronize(sl.released));
-    HIPCHK(c, sl.d_f.reserve(fbytes / sizeof(double)));
+    HIPCHK(c, sl.d_f.reserve(nf));
     HIPCHK(c, sl.d_s.reserve(sbytes));
-    HIPCHK(c, sl.d_raw.reserve(rbytes / sizeof(double)));
+    HIPCHK(c, sl.d_raw.reserve(nraw));
   }
   const size_t need_stage = raw ? (is_pinned(raw) ? 0 : rbytes) : ((is_pinned(forcing) ? 0 : fbytes) + (is_pinned(snowflag) ? 0 : sbytes));
   HIPCHK(c, sl.h_stage.reserve(need_stage));
@@ -416,10 +285,11 @@ int vicgpu_get_forcing(vicgpu_ctx* c, int step, double* forcing, unsigned char* 
   if (!c || !forcing || !snowflag) return VICGPU_ERR_ARG;
   if (c->cur < 0 || step < 0 || step >= c->chunk_steps) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t nsub = c->o.NR + 1;
+  const size_t nflag = (size_t)(c->o.NR + 1) * c->dom.ncell, nforce = VIC_NFORCE * nflag;      // of one step
+  const vicgpu_ctx::ForcingSlot& sl = c->slot[c->cur];      // d_forcing / d_snowflag are views of its buffers
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, forcing, c->d_forcing + (size_t)step * VIC_NFORCE * nsub * c->dom.ncell, sizeof(double) * VIC_NFORCE * nsub * c->dom.ncell, hipMemcpyDeviceToHost));
-  HIPCHK(c, copy_on(c->stream, snowflag, c->d_snowflag + (size_t)step * nsub * c->dom.ncell, nsub * c->dom.ncell, hipMemcpyDeviceToHost));
+  HIPCHK(c, sl.d_f.download(c->stream, forcing, step * nforce, nforce));
+  HIPCHK(c, sl.d_s.download(c->stream, snowflag, step * nflag, nflag));
   return VICGPU_OK;
 }
 
@@ -514,36 +384,16 @@ int vicgpu_last_kernel_ms(vicgpu_ctx* c, double* ms_per_launch, int* nlaunch) {
   return VICGPU_OK;
 }
 
-static int d2h(vicgpu_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (!c || !dst || !src) return VICGPU_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, dst, src, bytes, hipMemcpyDeviceToHost));
-  return VICGPU_OK;
-}
-
-// the same for a per-cell table [nrow][ncell] into the columns [0, ncell) of a host table whose rows are ld cells wide (a group
-// reads one shard's columns straight into the caller's global table)
-static int d2h_cols(vicgpu_ctx* c, void* dst, int ld, const void* src, size_t elem, int nrow) {
-  if (!c || !dst || !src || ld < c->dom.ncell) return VICGPU_ERR_ARG;
-  if (ld == c->dom.ncell) return d2h(c, dst, src, elem * nrow * c->dom.ncell);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy2DAsync(dst, elem * ld, src, elem * c->dom.ncell, elem * c->dom.ncell, nrow, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VICGPU_OK;
-}
-
-int vicgpu_get_fluxes(vicgpu_ctx* c, double* flux) { return c ? d2h(c, flux, c->dom.d_flux, sizeof(double) * FX_NROW * c->dom.nhru) : VICGPU_ERR_ARG; }
-int vicgpu_get_cell_outputs(vicgpu_ctx* c, double* o) { return c ? d2h(c, o, c->dom.d_cell_out, sizeof(double) * CO_NROW * c->dom.ncell) : VICGPU_ERR_ARG; }
-int vicgpu_get_accum(vicgpu_ctx* c, double* a) { return c ? d2h(c, a, c->dom.d_accum, sizeof(double) * CA_NROW * c->dom.ncell) : VICGPU_ERR_ARG; }
-int vicgpu_get_cell_errors(vicgpu_ctx* c, int* f) { return c ? d2h(c, f, c->dom.d_cell_err, sizeof(int) * c->dom.ncell) : VICGPU_ERR_ARG; }
+int vicgpu_get_fluxes(vicgpu_ctx* c, double* flux) { return c ? d2h(c, flux, c->dom.d_flux) : VICGPU_ERR_ARG; }
+int vicgpu_get_cell_outputs(vicgpu_ctx* c, double* o) { return c ? d2h(c, o, c->dom.d_cell_out) : VICGPU_ERR_ARG; }
+int vicgpu_get_accum(vicgpu_ctx* c, double* a) { return c ? d2h(c, a, c->dom.d_accum) : VICGPU_ERR_ARG; }
+int vicgpu_get_cell_errors(vicgpu_ctx* c, int* f) { return c ? d2h(c, f, c->dom.d_cell_err) : VICGPU_ERR_ARG; }
 
 int vicgpu_reset_accum(vicgpu_ctx* c) {
   if (!c || !c->dom.d_accum) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemsetAsync(c->dom.d_accum, 0, sizeof(double) * CA_NROW * c->dom.ncell, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->dom.d_cell_err, 0, sizeof(int) * c->dom.ncell, c->stream));
+  HIPCHK(c, c->dom.d_accum.fill(c->stream, 0));
+  HIPCHK(c, c->dom.d_cell_err.fill(c->stream, 0));
   return VICGPU_OK;
 }
 
@@ -558,12 +408,7 @@ static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld) {
   hipLaunchKernelGGL(vic_glacier_fit, dim3((c->dom.ncell + 63) / 64), dim3(64), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (ld == c->dom.ncell) HIPCHK(c, copy_on(c->stream, eq, d_eq, sizeof(double) * GMB_NROW * c->dom.ncell, hipMemcpyDeviceToHost));
-  else {
-    HIPCHK(c, hipMemcpy2DAsync(eq, sizeof(double) * ld, d_eq, sizeof(double) * c->dom.ncell, sizeof(double) * c->dom.ncell, GMB_NROW,
-                               hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
+  HIPCHK(c, d_eq.download_cols(c->stream, eq, ld, GMB_NROW, c->dom.ncell));
   return VICGPU_OK;
 }
 int vicgpu_glacier_mass_balance_fit(vicgpu_ctx* c, double* eq, int reset) { return c ? glacier_fit_impl(c, eq, reset, c->dom.ncell) : VICGPU_ERR_ARG; }
@@ -574,13 +419,13 @@ int vicgpu_debug_pure(vicgpu_ctx* c, int fn, int n, const double* in, double* ou
   DevBuf<double> d_in, d_out;
   HIPCHK(c, d_in.alloc((size_t)n * VICGPU_PURE_NIN));
   HIPCHK(c, d_out.alloc(n));
-  HIPCHK(c, copy_on(c->stream, d_in, in, sizeof(double) * (size_t)n * VICGPU_PURE_NIN, hipMemcpyHostToDevice));
+  HIPCHK(c, d_in.upload(c->stream, in));
   DArgs d;
   d.o = c->o; d.cell_params = c->dom.d_cp; d.ncell = c->dom.ncell; d.fn = fn; d.n = n; d.in = d_in; d.out = d_out;
   hipLaunchKernelGGL(vic_debug_pure, dim3((n + 63) / 64), dim3(64), 0, c->stream, d);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(c, d_out.download(c->stream, out));
   return VICGPU_OK;
 }
 
@@ -600,9 +445,9 @@ int vicgpu_debug_root_brent(vicgpu_ctx* c, int mode, int n, const double* bounds
   HIPCHK(c, d_f.alloc(nvs));
   HIPCHK(c, d_x.alloc(nvs));
   HIPCHK(c, d_out.alloc((size_t)n * VICGPU_BRENT_NOUT));
-  HIPCHK(c, copy_on(c->stream, d_bounds, bounds, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(c, copy_on(c->stream, d_off, off, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
-  if (nv > 0) HIPCHK(c, copy_on(c->stream, d_f, fvals, sizeof(double) * (size_t)nv, hipMemcpyHostToDevice));
+  HIPCHK(c, d_bounds.upload(c->stream, bounds));
+  HIPCHK(c, d_off.upload(c->stream, off));
+  if (nv > 0) HIPCHK(c, d_f.upload(c->stream, fvals));
   RBArgs d;
   d.n = n; d.bounds = d_bounds; d.off = d_off; d.fvals = d_f; d.xreq = d_x; d.out = d_out;
   const dim3 grid((n + 63) / 64), block(64);
@@ -610,8 +455,8 @@ int vicgpu_debug_root_brent(vicgpu_ctx* c, int mode, int n, const double* bounds
   else hipLaunchKernelGGL((vic_debug_root_brent<BrentLean>), grid, block, 0, c->stream, d);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nv > 0) HIPCHK(c, copy_on(c->stream, xreq, d_x, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost));
-  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_BRENT_NOUT, hipMemcpyDeviceToHost));
+  if (nv > 0) HIPCHK(c, d_x.download(c->stream, xreq));
+  HIPCHK(c, d_out.download(c->stream, out));
   return VICGPU_OK;
 }
 
@@ -621,7 +466,7 @@ int vicgpu_debug_node_root(vicgpu_ctx* c, int mode, int n, const double* in, dou
   DevBuf<double> d_in, d_out;
   HIPCHK(c, d_in.alloc((size_t)n * VICGPU_NODE_NIN));
   HIPCHK(c, d_out.alloc((size_t)n * VICGPU_NODE_NOUT));
-  HIPCHK(c, copy_on(c->stream, d_in, in, sizeof(double) * (size_t)n * VICGPU_NODE_NIN, hipMemcpyHostToDevice));
+  HIPCHK(c, d_in.upload(c->stream, in));
   NRArgs d;
   d.n = n; d.EXP_TRANS = (mode & VICGPU_NODE_EXP_TRANS) != 0; d.in = d_in; d.out = d_out;
   const dim3 grid((n + 63) / 64), block(64);
@@ -633,7 +478,7 @@ int vicgpu_debug_node_root(vicgpu_ctx* c, int mode, int n, const double* in, dou
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, out, d_out, sizeof(double) * (size_t)n * VICGPU_NODE_NOUT, hipMemcpyDeviceToHost));
+  HIPCHK(c, d_out.download(c->stream, out));
   return VICGPU_OK;
 }
 
@@ -670,35 +515,33 @@ static int state_records(vicgpu_ctx* c, double* host, bool gather) {
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t nrec = (size_t)VICGPU_SR_LEN(c->opt.Nnode) * c->dom.nhru, bytes = sizeof(double) * nrec;
+  const size_t L = VICGPU_SR_LEN(c->opt.Nnode), nhru = c->dom.nhru;
   DevBuf<double> d_rec;
   DevBuf<int> d_mis;
-  HIPCHK(c, d_rec.alloc(nrec));
-  HIPCHK(c, d_mis.alloc(1));
-  HIPCHK(c, fill_on(c->stream, d_mis, 0, sizeof(int)));
-  if (!gather) HIPCHK(c, copy_on(c->stream, d_rec, host, bytes, hipMemcpyHostToDevice));
+  HIPCHK(c, d_rec.alloc(L * nhru));
+  HIPCHK(c, d_mis.alloc_fill(1, 0, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!gather) HIPCHK(c, d_rec.upload(c->stream, host));
   RArgs a;
   a.nhru = c->dom.nhru; a.Nn = c->opt.Nnode; a.cell_list = c->dom.d_cell_list; a.hpi = c->dom.d_hpi; a.sd = c->dom.d_sd; a.si = c->dom.d_si;
   a.flux = c->dom.d_flux; a.rec = d_rec; a.mismatch = d_mis;
   if (!gather) {
     // read side, pass 1: validate every record before anything is scattered (a reader that throws changes nothing)
-    std::vector<int> hpi_band(c->dom.nhru), hpi_veg(c->dom.nhru), list(c->dom.nhru);
-    HIPCHK(c, copy_on(c->stream, hpi_band.data(), c->dom.d_hpi + (size_t)HPI_BAND * c->dom.nhru, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_on(c->stream, hpi_veg.data(), c->dom.d_hpi + (size_t)HPI_VEG_CLASS * c->dom.nhru, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
-    HIPCHK(c, copy_on(c->stream, list.data(), c->dom.d_cell_list, sizeof(int) * c->dom.nhru, hipMemcpyDeviceToHost));
-    const size_t L = VICGPU_SR_LEN(c->opt.Nnode);
-    for (int k = 0; k < c->dom.nhru; k++)
-      if ((int)host[k * L + SR_BAND_INDEX] != hpi_band[list[k]] || (int)host[k * L + SR_VEG_CLASS] != hpi_veg[list[k]]) {
-        c->err = "state record " + std::to_string(k) + ": band / vegetation class do not match the domain (write_model_state.c:179-188)";
-        return VICGPU_ERR_ARG;
-      }
+    std::vector<int> hpi_band(nhru), hpi_veg(nhru), list(nhru);
+    HIPCHK(c, c->dom.d_hpi.download(c->stream, hpi_band.data(), HPI_BAND * nhru, nhru));
+    HIPCHK(c, c->dom.d_hpi.download(c->stream, hpi_veg.data(), HPI_VEG_CLASS * nhru, nhru));
+    HIPCHK(c, c->dom.d_cell_list.download(c->stream, list.data()));
+    for (size_t k = 0; k < nhru; k++) {
+      c->err = check_state_record(host + k * L, k, hpi_band[list[k]], hpi_veg[list[k]]);
+      if (!c->err.empty()) return VICGPU_ERR_ARG;
+    }
   }
   const unsigned nblk = (unsigned)((c->dom.nhru + 255) / 256);
   if (gather) hipLaunchKernelGGL(vic_state_records<true>, dim3(nblk), dim3(256), 0, c->stream, a);
   else hipLaunchKernelGGL(vic_state_records<false>, dim3(nblk), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (gather) HIPCHK(c, copy_on(c->stream, host, d_rec, bytes, hipMemcpyDeviceToHost));
+  if (gather) HIPCHK(c, d_rec.download(c->stream, host));
   return VICGPU_OK;
 }
 int vicgpu_get_state_records(vicgpu_ctx* c, double* rec) { return state_records(c, rec, true); }
@@ -749,14 +592,15 @@ int vicgpu_put_data_config(vicgpu_ctx* c, int out_step_ratio) {
     DevBuf<unsigned char> d_rowagg;
     HIPCHK(c, out_data.alloc((size_t)r * c->dom.ncell));
     HIPCHK(c, out_agg.alloc((size_t)r * c->dom.ncell));
-    HIPCHK(c, pb.alloc((size_t)PBX_NROW * c->dom.ncell));
+    HIPCHK(c, pb.alloc((size_t)PBX_NROW * c->dom.ncell));                  // the public PB_NROW rows + put_data's own
     HIPCHK(c, d_rowagg.alloc(r));
     c->dom.d_out_data = std::move(out_data); c->dom.d_out_agg = std::move(out_agg); c->dom.d_pb = std::move(pb); c->dom.d_rowagg = std::move(d_rowagg);
   }
-  HIPCHK(c, copy_on(c->stream, c->dom.d_rowagg, rowagg.data(), (size_t)r, hipMemcpyHostToDevice));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_out_data, 0, sizeof(double) * (size_t)r * c->dom.ncell));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_out_agg, 0, sizeof(double) * (size_t)r * c->dom.ncell));
-  HIPCHK(c, fill_on(c->stream, c->dom.d_pb, 0, sizeof(double) * (size_t)PBX_NROW * c->dom.ncell));
+  HIPCHK(c, c->dom.d_rowagg.upload(c->stream, rowagg.data()));
+  HIPCHK(c, c->dom.d_out_data.fill(c->stream, 0));
+  HIPCHK(c, c->dom.d_out_agg.fill(c->stream, 0));
+  HIPCHK(c, c->dom.d_pb.fill(c->stream, 0));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   c->dom.put_on = true;
   return VICGPU_OK;
 }
@@ -793,20 +637,18 @@ static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* 
     const size_t n = (size_t)nr * c->dom.ncell;
     HIPCHK(c, d_rows.alloc(nr));
     HIPCHK(c, d_f.alloc(n));
-    HIPCHK(c, copy_on(c->stream, d_rows, rows.data(), sizeof(int) * nr, hipMemcpyHostToDevice));
+    HIPCHK(c, d_rows.upload(c->stream, rows.data()));
     const int* rows_arg = d_rows;
     float* f_arg = d_f;
     hipLaunchKernelGGL(vic_out_rows_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->dom.d_out_agg, rows_arg, nr,
                        c->dom.ncell, f_arg);
     HIPCHK(c, hipGetLastError());
-    if (ld == c->dom.ncell) HIPCHK(c, copy_on(c->stream, out, d_f, sizeof(float) * n, hipMemcpyDeviceToHost));
-    else {
-      HIPCHK(c, hipMemcpy2DAsync(out, sizeof(float) * ld, d_f, sizeof(float) * c->dom.ncell, sizeof(float) * c->dom.ncell, nr,
-                                 hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    HIPCHK(c, d_f.download_cols(c->stream, out, ld, nr, c->dom.ncell));
   }
-  if (reset) HIPCHK(c, fill_on(c->stream, c->dom.d_out_agg, 0, sizeof(double) * (size_t)c->dom.out_nrow * c->dom.ncell));   // vicNl.c:599-606
+  if (reset) {                     // vicNl.c:599-606
+    HIPCHK(c, c->dom.d_out_agg.fill(c->stream, 0));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   return VICGPU_OK;
 }
 int vicgpu_get_outputs(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset) {
@@ -818,11 +660,12 @@ int vicgpu_get_output_data(vicgpu_ctx* c, int nvar, const int* var_ids, int whic
   if (!c->dom.put_on) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  const DevBuf<double>& table = which ? c->dom.d_out_agg : c->dom.d_out_data;
   size_t at = 0;
   for (int k = 0; k < nvar; k++) {
     if (var_ids[k] < 0 || var_ids[k] >= VOUT_NVAR) return VICGPU_ERR_ARG;
     const int r0 = c->dom.out_lay.off[var_ids[k]], ne = c->dom.out_lay.off[var_ids[k] + 1] - r0;
-    HIPCHK(c, copy_on(c->stream, out + at, (which ? c->dom.d_out_agg : c->dom.d_out_data) + (size_t)r0 * c->dom.ncell, sizeof(double) * (size_t)ne * c->dom.ncell, hipMemcpyDeviceToHost));
+    HIPCHK(c, table.download(c->stream, out + at, (size_t)r0 * c->dom.ncell, (size_t)ne * c->dom.ncell));
     at += (size_t)ne * c->dom.ncell;
   }
   return VICGPU_OK;
@@ -831,7 +674,7 @@ int vicgpu_get_output_data(vicgpu_ctx* c, int nvar, const int* var_ids, int whic
 int vicgpu_get_balance(vicgpu_ctx* c, double* pb) {
   if (!c || !pb) return VICGPU_ERR_ARG;
   if (!c->dom.put_on) return VICGPU_ERR_STATE;
-  return d2h(c, pb, c->dom.d_pb, sizeof(double) * (size_t)PB_NROW * c->dom.ncell);
+  return d2h(c, pb, c->dom.d_pb, (size_t)PB_NROW * c->dom.ncell);      // the public rows of PBX_NROW
 }
 
 int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
@@ -839,7 +682,7 @@ int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, copy_on(c->stream, c->dom.d_flux, flux, sizeof(double) * FX_NROW * c->dom.nhru, hipMemcpyHostToDevice));
+  HIPCHK(c, c->dom.d_flux.upload(c->stream, flux));
   return VICGPU_OK;
 }
 
