@@ -137,6 +137,31 @@ int vicgpu_get_balance(vicgpu_ctx *ctx, double *pb);     /* [PB_NROW][ncell] */
 int vicgpu_set_fluxes(vicgpu_ctx *ctx, const double *flux);   /* [FX_NROW][nhru]: the per-HRU values put_data reads that the
                                                                  reference carries from initialize_model_state (see FX_*) */
 
+/* Output records without a host round trip per record.  R = the out_step_ratio of vicgpu_put_data_config.
+ *
+ * vicgpu_run_records(step0, nrecords) is, for every k in [0, nrecords), bit for bit
+ *     vicgpu_step(ctx, step0 + k*R, R); vicgpu_get_outputs(ctx, nvar, var_ids, out[k], 1); vicgpu_get_cell_errors(ctx, cell_err[k]);
+ * but record k travels to the host, on a stream the steps do not use, while the steps of record k+1 run: after the last step of a
+ * record one kernel packs the selected aggregates as floats into one of `depth` device slots and zeroes every aggregate
+ * (vicNl.c:599-606), and the slot is copied into out[k] / cell_err[k] behind it.  Record 0 includes what the aggregates
+ * held before the call; state, fluxes, accumulators, vicgpu_get_balance and vicgpu_last_kernel_ms (the steps of the last
+ * record) are left as the loop leaves them, the aggregates are zero.  Results do not depend on depth.
+ * With QUICK_FLUX the call only enqueues, like vicgpu_step; with the finite-difference pipeline it blocks like
+ * vicgpu_step, every cell chunk delivering its own columns at its own record boundaries.  out[k] and cell_err[k] may be read
+ * once vicgpu_records_wait(ctx, k) has returned (k = -1: every record of the last call); vicgpu_synchronize waits for
+ * them all too.  out and cell_err must be pinned memory (vicgpu_host_alloc) and stay allocated until then.
+ *
+ * VICGPU_ERR_STATE: put_data or records not configured (vicgpu_put_data_config and vicgpu_set_domain drop the records
+ * configuration), no forcing chunk loaded, vicgpu_records_wait before any vicgpu_run_records.  VICGPU_ERR_ARG: depth < 1, an
+ * id out of range or listed twice, nrecords < 1, step0 + nrecords*R past the chunk, out or cell_err not pinned, k outside
+ * the last call.  On an error return no copy is in flight.  nvar = 0 releases the slots. */
+int vicgpu_records_config(vicgpu_ctx *ctx, int nvar, const int *var_ids, int depth);
+int vicgpu_records_nrow(vicgpu_ctx *ctx);              /* sum of nelem of the selected variables; <0 = error code */
+int vicgpu_run_records(vicgpu_ctx *ctx, int step0, int nrecords,
+                       float *out,                     /* [nrecords][nrow][ncell], from vicgpu_host_alloc */
+                       int *cell_err);                 /* [nrecords][ncell] from vicgpu_host_alloc, or NULL */
+int vicgpu_records_wait(vicgpu_ctx *ctx, int k);       /* record k of the last vicgpu_run_records has landed; k = -1: all */
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,10 @@ def load_library():
         "vicgpu_get_output_data": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _dp]),
         "vicgpu_get_balance": (ctypes.c_int, [vp, _dp]),
         "vicgpu_set_fluxes": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_records_config": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
+        "vicgpu_records_nrow": (ctypes.c_int, [vp]),
+        "vicgpu_run_records": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), _ip]),
+        "vicgpu_records_wait": (ctypes.c_int, [vp, ctypes.c_int]),
         # include/vicgpu_group.h
         "vicgpu_group_partition": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, _ip]),
         "vicgpu_group_create": (ctypes.c_int, [ctypes.POINTER(abi.Options), ctypes.c_int, _ip, ctypes.POINTER(vp)]),
@@ -113,6 +117,10 @@ def load_library():
         "vicgpu_group_get_state_records": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_set_state_records": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
+        "vicgpu_group_records_config": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
+        "vicgpu_group_records_nrow": (ctypes.c_int, [vp]),
+        "vicgpu_group_run_records": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), _ip]),
+        "vicgpu_group_records_wait": (ctypes.c_int, [vp, ctypes.c_int]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -129,6 +137,7 @@ GROUP_ENTRIES = [
     "destroy", "last_error", "set_veglib", "set_domain", "set_state", "get_state", "set_fluxes", "get_fluxes", "push_forcing",
     "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
+    "records_config", "records_nrow", "run_records", "records_wait",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -140,6 +149,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_out_nvar", "vicgpu_out_var_id", "vicgpu_out_var_name", "vicgpu_out_var_kind", "vicgpu_out_var_agg", "vicgpu_out_var_nelem",
     "vicgpu_put_data_config", "vicgpu_put_data_init", "vicgpu_get_outputs", "vicgpu_get_output_data", "vicgpu_get_balance",
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
+    "vicgpu_records_config", "vicgpu_records_nrow", "vicgpu_run_records", "vicgpu_records_wait",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
@@ -151,6 +161,44 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+class Records:
+    """The records of one Model.run_records call: `.out` float32 [nrecords][nrow][ncell] and `.errors` int32 [nrecords][ncell]
+    (None unless asked for) over pinned memory that the copies land in while later records are still being computed.
+    Record k may be read after `wait(k)`, everything after `wait()`.  The memory lives as long as this object."""
+
+    def __init__(self, model, nrecords, nrow, errors):
+        self._model = model          # keeps the library and the context alive while copies may be in flight
+        self._lib = model.lib
+        self._ptrs = []
+        self.nrecords = nrecords
+        self.out = self._pinned((nrecords, nrow, model.dom.ncell), np.float32)
+        self.errors = self._pinned((nrecords, model.dom.ncell), np.int32) if errors else None
+
+    def _pinned(self, shape, dtype):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        p = self._lib.vicgpu_host_alloc(n)
+        if not p:
+            raise VicGpuError("vicgpu_host_alloc(%d) failed" % n)
+        self._ptrs.append(p)
+        return np.frombuffer((ctypes.c_char * n).from_address(p), dtype=dtype).reshape(shape)
+
+    def wait(self, k=None):
+        """Blocks until record k (None: every record) is in `.out` / `.errors`."""
+        m = self._model
+        m._chk(m.lib.vicgpu_records_wait(m.h, -1 if k is None else int(k)))
+
+    def __del__(self):
+        try:
+            m = self._model
+            if self._ptrs and getattr(m, "h", None):
+                m.lib.vicgpu_synchronize(m.h)       # no copy may still be writing into the memory
+            for p in self._ptrs:
+                self._lib.vicgpu_host_free(p)
+            self._ptrs = []
+        except Exception:
+            pass
 
 
 class Model:
@@ -342,6 +390,22 @@ class Model:
         out = np.zeros((self._out_rows(ids), self.dom.ncell))
         self._chk(self.lib.vicgpu_get_output_data(self.h, len(ids), _i(ids), int(bool(aggregated)), _d(out)))
         return out
+
+    # ---- output records without a host round trip per record (vicgpu_run_records)
+    def records_config(self, names, depth=2):
+        """Selects the variables of the records and allocates `depth` device slots; an empty list releases them."""
+        ids = self.var_ids(names) if len(names) else np.zeros(0, dtype=np.int32)
+        self._chk(self.lib.vicgpu_records_config(self.h, len(ids), _i(ids), int(depth)))
+
+    def run_records(self, step0, nrecords, errors=False):
+        """nrecords output records from step step0 of the chunk, out_step_ratio steps each: what dist_prec + get_outputs(reset=True)
+        + get_cell_errors give record by record, delivered while the following records run.  Returns a Records."""
+        nrow = self.lib.vicgpu_records_nrow(self.h)
+        self._chk(min(nrow, 0))
+        rec = Records(self, int(nrecords), nrow, errors)
+        self._chk(self.lib.vicgpu_run_records(self.h, int(step0), int(nrecords), rec.out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                              _i(rec.errors) if errors else None))
+        return rec
 
     def get_balance(self):
         pb = np.zeros((C["PB_NROW"], self.dom.ncell))

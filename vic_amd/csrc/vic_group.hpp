@@ -19,6 +19,7 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
                          const int* dmy, double min_wind, int plapse, int ld);
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
+static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld);
 
 // One persistent host thread per shard.  run(fn) calls fn(k) on thread k for every shard and returns when all have returned.
 // Each thread selects its shard's device once at start (every library entry selects it again anyway).
@@ -388,6 +389,37 @@ int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset
   if (!g || !eq) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) { return glacier_fit_impl(g->ctx[k], eq + g->c0(k), reset, g->ncell); });
+}
+
+// Output records (vicgpu_out.h): every shard packs its own records and copies its columns into the caller's global tables
+int vicgpu_group_records_config(vicgpu_group* g, int nvar, const int* var_ids, int depth) {
+  if (!g || nvar < 0 || (nvar > 0 && !var_ids)) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return vicgpu_records_config(g->ctx[k], nvar, var_ids, depth); });
+}
+
+int vicgpu_group_records_nrow(vicgpu_group* g) {
+  if (!g) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return vicgpu_records_nrow(g->ctx[0]);             // the same selection on every shard
+}
+
+int vicgpu_group_run_records(vicgpu_group* g, int step0, int nrecords, float* out, int* cell_err) {
+  if (!g || !out) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  // the shards make the same checks on the same arguments before they queue anything, so either all of them run or none
+  const int r = group_each(g, [&](int k) {
+    return run_records_impl(g->ctx[k], step0, nrecords, out + g->c0(k), cell_err ? cell_err + g->c0(k) : nullptr, g->ncell);
+  });
+  if (r != VICGPU_OK)              // a shard that did start must leave no copy in flight either
+    for (vicgpu_ctx* c : g->ctx) vicgpu_synchronize(c);
+  return r;
+}
+
+int vicgpu_group_records_wait(vicgpu_group* g, int k) {
+  if (!g) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int s) { return vicgpu_records_wait(g->ctx[s], k); });
 }
 
 // State records: shard k's records are the global records [cell_hru_offset[b[k]], cell_hru_offset[b[k+1]]), in the same order

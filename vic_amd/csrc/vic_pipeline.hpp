@@ -1,7 +1,8 @@
 // vic_pipeline.hpp — the host pipeline: the context (vicgpu_ctx), its tuning variables (Tuning), what lives as long as a
 // domain (Domain, FdChunk) and the steps of vicgpu_set_domain that fill it, the kernel-argument structs filled from them,
-// the launchers, and the step of the finite-difference pipeline (fd_step: the round loop; fd_chunk_run: all steps of one
-// vicgpu_step call for one cell chunk).  Host code only, no kernels.
+// the launchers, the step of the finite-difference pipeline (fd_step: the round loop; fd_chunk_run: all steps of one
+// vicgpu_step or vicgpu_run_records call for one cell chunk) and the end of an output record (Records, records_emit).
+// Host code only, no kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -20,6 +21,7 @@
 #include "vic_hru_io.hpp"
 #include "vic_kernels.hpp"
 #include "vic_aux_kernels.hpp"
+#include "vic_records.hpp"
 
 using namespace vic;
 
@@ -127,6 +129,35 @@ static Tuning read_tuning(int node_solver, int ncell) {
   return t;
 }
 
+// Output records (vicgpu_records_config / vicgpu_run_records): the selection, a ring of `depth` device slots and the events
+// that order the packing kernel on the stream that ran a record's steps against the slot's copy on the download stream.
+// A lane is what delivers columns on its own: the context's stream (QUICK_FLUX) or a cell chunk of the finite-difference
+// pipeline.  Lives as long as the put_data configuration it was made for.
+// The download stream: with QUICK_FLUX a stream of its own (`dl`; the copy stream carries the next forcing chunk, which would
+// delay a record).  In the finite-difference pipeline the context's stream, which is idle while the chunks' streams run the
+// steps: a fifth stream made two of them share one of the process's four hardware queues, and the two chunks of a 100k-cell
+// domain then ran one after the other (28.9 instead of 22.1 ms per step).
+struct Records {
+  int nrow = 0, depth = 0;         // rows of a record; depth == 0: not configured
+  DevBuf<int> d_sel_pos;           // [out_nrow]: the record row of an aggregate row, or -1
+  struct Slot {
+    DevBuf<float> d_out;           // [nrow][ncell]
+    DevBuf<int> d_err;             // [ncell]
+  };
+  std::vector<Slot> slot;
+  int nlane = 0;
+  std::vector<Event> packed;       // [nlane][depth]: the slot holds the lane's columns of its record
+  std::vector<Event> landed;       // [nlane][records of the largest call]: the lane's columns of record k are in the caller's tables
+  Stream dl;                       // QUICK_FLUX only
+  Event drained;                   // download stream: every copy of the last call has been made
+  int last_nrecords = 0;           // of the last vicgpu_run_records; 0: none yet
+  bool follows = false;            // the call in flight follows another one, whose copies may still read the slots
+  // the call in flight (set by vicgpu_run_records before the lanes start, read by them)
+  float* out = nullptr;
+  int* err = nullptr;
+  int ld = 0;                      // cells per row of out / err
+};
+
 struct vicgpu_ctx {
   vicgpu_options opt;
   Opt o;
@@ -155,6 +186,7 @@ struct vicgpu_ctx {
   } slot[2];
   int cur = -1, staged = -1;
   Stream stream, copy_stream;      // `stream` may be borrowed (vicgpu_set_stream)
+  Records rec;
   std::vector<Event> ev;           // start/stop pairs of the last vicgpu_step call
   int ev_used = 0;
   int write_fluxes = 1;
@@ -164,7 +196,17 @@ struct vicgpu_ctx {
   int out_step_ratio = 1;
 };
 
+// the stream that carries the output records to the host (see Records)
+static hipStream_t records_stream(const vicgpu_ctx* c) { return c->rec.dl ? (hipStream_t)c->rec.dl : (hipStream_t)c->stream; }
+
+// Drops the records configuration; nothing may be left on the download stream
+static void free_records(vicgpu_ctx* c) {
+  if (c->rec.depth > 0) HIPIGN(hipStreamSynchronize(records_stream(c)));
+  c->rec = Records();
+}
+
 static void free_domain(vicgpu_ctx* c) {
+  free_records(c);
   c->dom = Domain();
   c->chunk_steps = 0;              // a forcing chunk belongs to the domain it was pushed for (its rows are ncell wide)
   c->dmy.clear();
@@ -409,12 +451,46 @@ static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, i
   return hipGetLastError();
 }
 
+// nsteps steps from step0; with records, an output record ends after every `ratio` of them (nsteps = nrecords * ratio)
 struct StepPlan {
   vicgpu_ctx* c;
   KArgs ka;
   CArgs ca;
   int step0, nsteps;
+  bool records = false;
+  int ratio = 0;
 };
+
+// The end of record k for the cells [c0, c0 + ccount) of one lane, whose steps ran on `st`: once the slot's previous record
+// has been downloaded, pack the aggregates into slot k % depth and zero them; the download stream copies the lane's
+// columns into the caller's tables behind that.
+static hipError_t records_emit(vicgpu_ctx* c, int lane, hipStream_t st, int c0, int ccount, int k) {
+  Records& R = c->rec;
+  const hipStream_t dl = records_stream(c);
+  const int s = k % R.depth;
+  const size_t nc = c->dom.ncell, ld = R.ld;
+  hipError_t e = hipSuccess;
+  if (k >= R.depth) e = hipStreamWaitEvent(st, R.landed[(size_t)lane * R.last_nrecords + (k - R.depth)], 0);
+  else if (R.follows) e = hipStreamWaitEvent(st, R.drained, 0);      // the slot's last user is a copy of the call before
+  if (e != hipSuccess) return e;
+  RPArgs a;
+  a.ncell = c->dom.ncell; a.nrow = c->dom.out_nrow; a.c0 = c0; a.ccount = ccount;
+  a.out_agg = c->dom.d_out_agg; a.sel_pos = R.d_sel_pos; a.cell_err = c->dom.d_cell_err;
+  a.slot_out = R.slot[s].d_out; a.slot_err = R.slot[s].d_err;
+  hipLaunchKernelGGL(vic_out_pack_reset, dim3((unsigned)((ccount + 63) / 64), (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const hipEvent_t packed = R.packed[(size_t)lane * R.depth + s];
+  if ((e = hipEventRecord(packed, st)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(dl, packed, 0)) != hipSuccess) return e;
+  float* dst = R.out + (size_t)k * R.nrow * ld + c0;
+  const float* src = R.slot[s].d_out + c0;
+  if ((size_t)ccount == nc && ld == nc) e = hipMemcpyAsync(dst, src, sizeof(float) * nc * R.nrow, hipMemcpyDeviceToHost, dl);
+  else e = hipMemcpy2DAsync(dst, sizeof(float) * ld, src, sizeof(float) * nc, sizeof(float) * ccount, R.nrow, hipMemcpyDeviceToHost, dl);
+  if (e != hipSuccess) return e;
+  if (R.err) e = hipMemcpyAsync(R.err + (size_t)k * ld + c0, R.slot[s].d_err + c0, sizeof(int) * ccount, hipMemcpyDeviceToHost, dl);
+  if (e != hipSuccess) return e;
+  return hipEventRecord(R.landed[(size_t)lane * R.last_nrecords + k], dl);
+}
 
 static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
   const size_t nsub = c->o.NR + 1;
@@ -425,7 +501,7 @@ static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
   ka.dmy.day = d[VIC_DMY_DAY]; ka.dmy.year = d[VIC_DMY_YEAR];
 }
 
-// all steps of one vicgpu_step call for one chunk
+// all steps of one vicgpu_step or vicgpu_run_records call for one chunk
 static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
   vicgpu_ctx* c = plan.c;
   HIPCHK(ch, hipSetDevice(c->device));
@@ -433,7 +509,11 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
   CArgs ca = plan.ca;
   ka.glist = ch->d_glist; ka.gcount = ch->gcount; ka.map = ch->map;
   ca.c0 = ch->c0; ca.ccount = ch->ccount;
+  const int lane = (int)(ch - &c->dom.chunks[0]);
   for (int s = plan.step0; s < plan.step0 + plan.nsteps; s++) {
+    // the event pair of vicgpu_last_kernel_ms covers the last record, as after the loop of vicgpu_step calls: from where
+    // the first chunk starts it
+    if (plan.records && lane == 0 && s == plan.step0 + plan.nsteps - plan.ratio && s > plan.step0) HIPCHK(ch, hipEventRecord(c->ev[0], ch->stream));
     set_step_inputs(c, ka, s);
     const long long r0 = ch->rounds;
     const auto t0 = std::chrono::steady_clock::now();
@@ -447,6 +527,8 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
     hipLaunchKernelGGL(vic_cell_reduce, dim3((ch->ccount + 255) / 256), dim3(256), 0, ch->stream, ca);
     HIPCHK(ch, hipGetLastError());
     if (c->dom.put_on) HIPCHK(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
+    if (plan.records && (s - plan.step0 + 1) % plan.ratio == 0)
+      HIPCHK(ch, records_emit(c, lane, ch->stream, ch->c0, ch->ccount, (s - plan.step0) / plan.ratio));
   }
   HIPCHK(ch, hipEventRecord(ch->done, ch->stream));
   return VICGPU_OK;

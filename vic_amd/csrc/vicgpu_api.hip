@@ -7,6 +7,7 @@
 //   vic_hru_io.hpp       KArgs, LaunchMap and the HRU table I/O
 //   vic_kernels.hpp      vic_hru_step, vic_fd_stage, vic_surf_eval
 //   vic_aux_kernels.hpp  glacier fit, derived cell rows, test hooks, vic_cell_reduce, state records, forcing derivation
+//   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records)
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -35,6 +36,7 @@
 #include "vic_hru_io.hpp"
 #include "vic_kernels.hpp"
 #include "vic_aux_kernels.hpp"
+#include "vic_records.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -109,6 +111,7 @@ void vicgpu_destroy(vicgpu_ctx* c) {
   HIPIGN(hipSetDevice(c->device));
   if (c->stream) HIPIGN(hipStreamSynchronize(c->stream));
   if (c->copy_stream) HIPIGN(hipStreamSynchronize(c->copy_stream));
+  if (c->rec.dl) HIPIGN(hipStreamSynchronize(c->rec.dl));
   if (c->tune.stats)
     for (size_t k = 0; k < c->dom.chunks.size(); k++)
       if (c->dom.chunks[k].steps)
@@ -299,12 +302,12 @@ void* vicgpu_host_alloc(size_t bytes) {
 }
 void vicgpu_host_free(void* p) { PinnedBuf<char> b((char*)p); }
 
-int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
-  if (!c) return VICGPU_ERR_ARG;
-  if (!c->dom.domain_ready || !c->d_veglib || !c->d_forcing || c->chunk_steps <= 0) return VICGPU_ERR_STATE;
-  if (step0 < 0 || nsteps <= 0 || step0 + nsteps > c->chunk_steps) return VICGPU_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  while ((int)c->ev.size() < 2 * nsteps) {
+// vicgpu_step (ratio = 0), or the steps of vicgpu_run_records: nsteps = nrecords * ratio, an output record ends after every
+// `ratio` steps (c->rec describes the call).  The event pairs of vicgpu_last_kernel_ms cover the steps of the last record.
+static int step_impl(vicgpu_ctx* c, int step0, int nsteps, int ratio) {
+  const bool records = ratio > 0;
+  const int per = records ? ratio : nsteps;          // steps the event pairs cover
+  while ((int)c->ev.size() < 2 * per) {
     Event e;
     HIPCHK(c, e.create());
     c->ev.push_back(std::move(e));
@@ -312,24 +315,26 @@ int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
   c->ev_used = 0;
   c->ev_steps = 0;
   StepPlan plan;
-  plan.c = c; plan.step0 = step0; plan.nsteps = nsteps;
+  plan.c = c; plan.step0 = step0; plan.nsteps = nsteps; plan.records = records; plan.ratio = ratio;
   plan.ka = make_kargs(c); plan.ca = make_cargs(c);
   KArgs& ka = plan.ka;
   const CArgs& ca = plan.ca;
   if (!c->dom.fd) {
     // QUICK_FLUX (implies Nnode == 3, vicgpu_create): one kernel per step, enqueued without blocking
     for (int s = step0; s < step0 + nsteps; s++) {
+      const int i = (s - step0) % per;
       set_step_inputs(c, ka, s);
-      HIPCHK(c, hipEventRecord(c->ev[2 * (s - step0)], c->stream));
+      HIPCHK(c, hipEventRecord(c->ev[2 * i], c->stream));
       HIPCHK(c, launch_hru<3>(ka, c->stream, true, c->dom.any_glacier));
-      HIPCHK(c, hipEventRecord(c->ev[2 * (s - step0) + 1], c->stream));
+      HIPCHK(c, hipEventRecord(c->ev[2 * i + 1], c->stream));
       hipLaunchKernelGGL(vic_cell_reduce, dim3((c->dom.ncell + 255) / 256), dim3(256), 0, c->stream, ca);
       HIPCHK(c, hipGetLastError());
       if (c->dom.put_on) HIPCHK(c, launch_put_data(c, c->stream, 0, c->dom.ncell, s));
       c->steps_done++;
+      if (records && i == per - 1) HIPCHK(c, records_emit(c, 0, c->stream, 0, c->dom.ncell, (s - step0) / per));
     }
-    c->ev_used = nsteps;
-    c->ev_steps = nsteps;
+    c->ev_used = per;
+    c->ev_steps = per;
     return VICGPU_OK;
   }
   // finite-difference pipeline: every chunk runs all nsteps on its own stream (ordered after what is queued on the
@@ -357,15 +362,24 @@ int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
   for (FdChunk& ch : c->dom.chunks) HIPCHK(c, hipStreamWaitEvent(c->stream, ch.done, 0));
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   c->ev_used = 1;
-  c->ev_steps = nsteps;
+  c->ev_steps = per;
   c->steps_done += nsteps;
   return VICGPU_OK;
+}
+
+int vicgpu_step(vicgpu_ctx* c, int step0, int nsteps) {
+  if (!c) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready || !c->d_veglib || !c->d_forcing || c->chunk_steps <= 0) return VICGPU_ERR_STATE;
+  if (step0 < 0 || nsteps <= 0 || step0 + nsteps > c->chunk_steps) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  return step_impl(c, step0, nsteps, 0);
 }
 
 int vicgpu_synchronize(vicgpu_ctx* c) {
   if (!c) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->rec.dl) HIPCHK(c, hipStreamSynchronize(c->rec.dl));      // the output records queued behind the steps (vicgpu_run_records)
   return VICGPU_OK;
 }
 
@@ -568,6 +582,7 @@ int vicgpu_put_data_config(vicgpu_ctx* c, int out_step_ratio) {
   if (!c->dom.domain_ready || !c->d_veglib) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_records(c);                 // a records configuration belongs to the output layout it was made for
   // the tree-line adjustment factor of every band (a function of the domain and the vegetation library's overstory flags)
   hipLaunchKernelGGL(vic_derive_tree_adjust, dim3((c->dom.ncell + 63) / 64), dim3(64), 0, c->stream, c->dom.d_cp, c->dom.ncell, c->dom.nhru, c->opt.Nnode,
                      c->opt.Nband, c->dom.d_cell_off, c->dom.d_cell_list, c->dom.d_hpi, c->dom.d_hpd, c->d_veglib);
@@ -683,6 +698,100 @@ int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, c->dom.d_flux.upload(c->stream, flux));
+  return VICGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ output records (vicgpu_out.h)
+int vicgpu_records_config(vicgpu_ctx* c, int nvar, const int* var_ids, int depth) {
+  if (!c) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (nvar == 0) {                 // releases the slots
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_records(c);
+    return VICGPU_OK;
+  }
+  if (!c->dom.put_on) return VICGPU_ERR_STATE;
+  if (nvar < 0 || !var_ids || depth < 1) return VICGPU_ERR_ARG;
+  std::vector<int> sel(c->dom.out_nrow, -1);
+  int nrow = 0;
+  for (int k = 0; k < nvar; k++) {
+    if (var_ids[k] < 0 || var_ids[k] >= VOUT_NVAR) return VICGPU_ERR_ARG;
+    for (int r = c->dom.out_lay.off[var_ids[k]]; r < c->dom.out_lay.off[var_ids[k] + 1]; r++) {
+      if (sel[r] >= 0) return VICGPU_ERR_ARG;        // listed twice
+      sel[r] = nrow++;
+    }
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // a record of the last call may still be on its way into a slot
+  free_records(c);
+  Records r;                       // becomes the context's only when complete
+  r.nrow = nrow; r.depth = depth;
+  HIPCHK(c, r.d_sel_pos.alloc(sel.size()));
+  HIPCHK(c, r.d_sel_pos.upload(c->stream, sel.data()));
+  r.slot.resize(depth);
+  for (Records::Slot& s : r.slot) {
+    HIPCHK(c, s.d_out.alloc((size_t)nrow * c->dom.ncell));
+    HIPCHK(c, s.d_err.alloc(c->dom.ncell));
+  }
+  r.nlane = c->dom.fd ? (int)c->dom.chunks.size() : 1;
+  r.packed.resize((size_t)r.nlane * depth);
+  for (Event& e : r.packed) HIPCHK(c, e.create(hipEventDisableTiming));
+  HIPCHK(c, r.drained.create(hipEventDisableTiming));
+  if (!c->dom.fd) HIPCHK(c, r.dl.create());
+  c->rec = std::move(r);
+  return VICGPU_OK;
+}
+
+int vicgpu_records_nrow(vicgpu_ctx* c) {
+  if (!c) return VICGPU_ERR_ARG;
+  return c->rec.depth > 0 ? c->rec.nrow : VICGPU_ERR_STATE;
+}
+
+// ld: cells per row of `out` and `cell_err` (c->dom.ncell, or the global cell count when a group delivers one shard's columns)
+static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld) {
+  if (!c) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready || !c->d_veglib || !c->dom.put_on || c->rec.depth < 1 || !c->d_forcing || c->chunk_steps <= 0) return VICGPU_ERR_STATE;
+  const int ratio = c->out_step_ratio;
+  if (step0 < 0 || nrecords < 1 || (long long)step0 + (long long)nrecords * ratio > c->chunk_steps || ld < c->dom.ncell) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!out || !is_pinned(out) || (cell_err && !is_pinned(cell_err))) return VICGPU_ERR_ARG;
+  Records& R = c->rec;
+  // record k's landed event of every lane
+  const size_t nev = (size_t)R.nlane * nrecords;
+  if (R.landed.size() < nev) {
+    const size_t had = R.landed.size();
+    R.landed.resize(nev);
+    for (size_t i = had; i < nev; i++) HIPCHK(c, R.landed[i].create(hipEventDisableTiming));
+  }
+  // the first packing kernels of this call reuse slots the last call's copies may still read: they wait for `drained`, which
+  // is recorded anew only after them (the steps themselves wait for nothing)
+  R.follows = R.last_nrecords > 0;
+  R.out = out; R.err = cell_err; R.ld = ld;
+  R.last_nrecords = nrecords;
+  int r = step_impl(c, step0, nrecords * ratio, ratio);
+  if (r == VICGPU_OK) {
+    const hipError_t e = hipEventRecord(R.drained, records_stream(c));
+    if (e != hipSuccess) { c->err = std::string("hipEventRecord: ") + hipGetErrorString(e); r = VICGPU_ERR_HIP; }
+  }
+  if (r != VICGPU_OK) {            // no copy stays in flight after an error return
+    HIPIGN(hipStreamSynchronize(c->stream));
+    for (FdChunk& ch : c->dom.chunks) HIPIGN(hipStreamSynchronize(ch.stream));
+    HIPIGN(hipStreamSynchronize(records_stream(c)));
+    R.last_nrecords = 0;
+  }
+  return r;
+}
+int vicgpu_run_records(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err) {
+  return c ? run_records_impl(c, step0, nrecords, out, cell_err, c->dom.ncell) : VICGPU_ERR_ARG;
+}
+
+int vicgpu_records_wait(vicgpu_ctx* c, int k) {
+  if (!c) return VICGPU_ERR_ARG;
+  const Records& R = c->rec;
+  if (R.depth < 1 || R.last_nrecords < 1) return VICGPU_ERR_STATE;
+  if (k < -1 || k >= R.last_nrecords) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (k < 0) { HIPCHK(c, hipEventSynchronize(R.drained)); return VICGPU_OK; }
+  for (int lane = 0; lane < R.nlane; lane++) HIPCHK(c, hipEventSynchronize(R.landed[(size_t)lane * R.last_nrecords + k]));
   return VICGPU_OK;
 }
 
