@@ -12,7 +12,9 @@
  * The entry points below are what a reference-side binding
  * calls instead of that loop body, once for ALL cells of a domain: plain
  * pointers and sizes, caller-owned host buffers, int return codes
- * (0 = ok, negative = error; VICGPU_ERR_*), never throws, never exits.
+ * (0 = ok, negative = error; VICGPU_ERR_*), never throws, never exits.  What that loop does with a cell whose step returned
+ * ERROR -- cell.isValid = FALSE, the cell skipped from the next record on (vicNl.c:521, 545-559; CONTINUEONERROR) -- is
+ * behind the boundary too: vicgpu_set_retire_on_error / vicgpu_set_cell_valid / vicgpu_get_cell_valid, decided on the device.
  *
  * Data contract.  Everything is struct-of-arrays ("tables"): a table is a
  * dense row-major double (or int) array [nrow][ncol] where the column is the
@@ -293,6 +295,7 @@ enum {
 #define VICGPU_CELLERR_AERO     2   /* CalcAerodynamic trunk-space error (CalcAerodynamic.c:214-217) */
 #define VICGPU_CELLERR_NODES    4   /* thermal nodes do not reach below the bottom layer (soil_conduction.c:526-529) */
 #define VICGPU_CELLERR_NAN      8   /* non-finite prognostic state after the step */
+#define VICGPU_CELLERR_REFERENCE (VICGPU_CELLERR_SOLVER | VICGPU_CELLERR_AERO | VICGPU_CELLERR_NODES)  /* the reference's ERROR returns */
 
 typedef struct vicgpu_ctx vicgpu_ctx;
 
@@ -401,6 +404,35 @@ int vicgpu_get_cell_outputs(vicgpu_ctx *ctx, double *cell_out);   /* [CO_NROW][n
 int vicgpu_get_accum(vicgpu_ctx *ctx, double *accum);             /* [CA_NROW][ncell] */
 int vicgpu_reset_accum(vicgpu_ctx *ctx);
 int vicgpu_get_cell_errors(vicgpu_ctx *ctx, int *flags);          /* [ncell] */
+
+/* ---- cell validity: cell.isValid and CONTINUEONERROR (vicNl.c:429, 521, 545-559) ----------
+ * The reference stops stepping a cell once its step has returned ERROR: isValid = FALSE (vicNl.c:545-559), and from the next
+ * record on vicNl.c:521 skips the cell entirely -- no dist_prec, no put_data, no accumulateGlacierMassBalance.  The cell
+ * keeps the state it failed in, and its aggregates, never refilled after the reset of vicNl.c:599-606, stay 0.
+ *   vicgpu_set_retire_on_error  mask = OR of VICGPU_CELLERR_*: a cell whose flag word has a bit of the mask set at the end of
+ *                               step s is invalid from step s + 1 on, decided on the device -- inside a multi-step vicgpu_step
+ *                               and inside vicgpu_run_records as well.  Step s itself is complete (every HRU, the cell sums,
+ *                               put_data: dist_prec.c:167 calls it after a failed full_energy too).  0 (the default): no cell is
+ *                               ever retired.  A setting of the context: it survives vicgpu_set_domain.
+ *   vicgpu_set_cell_valid       the host's own isValid, [ncell]: 0 = skip the cell from the next step on (a cell that failed
+ *                               initialisation, vicNl.c:429), vicgpu_put_data_init included; non-zero = step it again from the
+ *                               tables as they stand (a cell whose flag word still has a bit of the mask retires again after
+ *                               that step: vicgpu_reset_accum clears the flags).
+ *   vicgpu_get_cell_valid       [ncell], 1 = the next step computes the cell, 0 = it does not.
+ * Nothing of an invalid cell changes: the SD_* / SI_* / FX_* columns and hru_err of its HRUs (no zero record is written),
+ * its CO_* / CA_* columns (CA_NSTEPS included), its flag word, its PB_* bookkeeping and its un-aggregated output values.  Its
+ * aggregates receive nothing: after the next reset they are 0.0 in every row and stay so, as in the reference's files; an
+ * output record of such a cell holds those zeros and the frozen flag word.  Its glacier HRUs stop accumulating
+ * cum_mass_balance, and vicgpu_glacier_mass_balance_fit gives it the default equation without resetting them (vicNl.c:562).
+ * The validity table belongs to the domain: vicgpu_set_domain sets it to all 1; vicgpu_set_state and vicgpu_reset_accum
+ * leave it alone.  vicgpu_get_state_records / vicgpu_set_state_records keep their fixed [nhru] layout and include invalid
+ * cells; the reference leaves them out of the state file (vicNl.c:521 precedes write_model_state), so a driver filters the
+ * records with vicgpu_get_cell_valid.
+ * VICGPU_ERR_ARG: null handle or pointer, a mask with bits outside the four VICGPU_CELLERR_*; VICGPU_ERR_STATE: the validity
+ * entries before a domain is set. */
+int vicgpu_set_retire_on_error(vicgpu_ctx *ctx, int mask);        /* OR of VICGPU_CELLERR_*; 0 (default) = no cell is retired */
+int vicgpu_set_cell_valid(vicgpu_ctx *ctx, const int *valid);     /* [ncell], 0 = skip the cell from the next step on (cell.isValid) */
+int vicgpu_get_cell_valid(vicgpu_ctx *ctx, int *valid);           /* [ncell], 1 / 0 */
 
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */

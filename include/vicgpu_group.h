@@ -74,6 +74,11 @@ int vicgpu_group_put_data_init(vicgpu_group *g);
 int vicgpu_group_get_outputs(vicgpu_group *g, int nvar, const int *var_ids, float *out, int reset);
 int vicgpu_group_get_balance(vicgpu_group *g, double *pb);
 int vicgpu_group_get_cell_errors(vicgpu_group *g, int *flags);
+/* cell validity (vicgpu.h): the mask goes to every shard; the validity table is in the caller's global cell order and
+ * moves like the cell error flags */
+int vicgpu_group_set_retire_on_error(vicgpu_group *g, int mask);
+int vicgpu_group_set_cell_valid(vicgpu_group *g, const int *valid);
+int vicgpu_group_get_cell_valid(vicgpu_group *g, int *valid);
 int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);

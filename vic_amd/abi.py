@@ -41,6 +41,8 @@ def _parse_header(path):
 C = _parse_header(HEADER)
 # put_data's tables (include/vicgpu_out.h): the plain enums; the variable list itself is an X-macro, read from the library
 C.update(_parse_header(os.path.join(os.path.dirname(HEADER), "vicgpu_out.h")))
+# the one macro of the header that is an expression
+C["VICGPU_CELLERR_REFERENCE"] = C["VICGPU_CELLERR_SOLVER"] | C["VICGPU_CELLERR_AERO"] | C["VICGPU_CELLERR_NODES"]
 globals().update(C)
 
 VIC_NLAYER = C["VIC_NLAYER"]

@@ -57,6 +57,9 @@ def load_library():
         "vicgpu_get_accum": (ctypes.c_int, [vp, _dp]),
         "vicgpu_reset_accum": (ctypes.c_int, [vp]),
         "vicgpu_get_cell_errors": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_set_retire_on_error": (ctypes.c_int, [vp, ctypes.c_int]),
+        "vicgpu_set_cell_valid": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_get_cell_valid": (ctypes.c_int, [vp, _ip]),
         "vicgpu_set_stream": (ctypes.c_int, [vp, vp]),
         "vicgpu_set_write_fluxes": (ctypes.c_int, [vp, ctypes.c_int]),
         "vicgpu_device_ptr": (vp, [vp, ctypes.c_int]),
@@ -114,6 +117,9 @@ def load_library():
         "vicgpu_group_get_outputs": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),
         "vicgpu_group_get_balance": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_get_cell_errors": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_group_set_retire_on_error": (ctypes.c_int, [vp, ctypes.c_int]),
+        "vicgpu_group_set_cell_valid": (ctypes.c_int, [vp, _ip]),
+        "vicgpu_group_get_cell_valid": (ctypes.c_int, [vp, _ip]),
         "vicgpu_group_get_state_records": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_set_state_records": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
@@ -137,7 +143,7 @@ GROUP_ENTRIES = [
     "destroy", "last_error", "set_veglib", "set_domain", "set_state", "get_state", "set_fluxes", "get_fluxes", "push_forcing",
     "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
-    "records_config", "records_nrow", "run_records", "records_wait",
+    "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -151,7 +157,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
     "vicgpu_records_config", "vicgpu_records_nrow", "vicgpu_run_records", "vicgpu_records_wait",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
-    "vicgpu_host_free",
+    "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -341,6 +347,23 @@ class Model:
         ce = np.zeros(self.dom.ncell, dtype=np.int32)
         self._chk(self.lib.vicgpu_get_cell_errors(self.h, _i(ce)))
         return ce
+
+    # ---- cell validity: cell.isValid and CONTINUEONERROR (vicNl.c:429, 521, 545-559)
+    def set_retire_on_error(self, mask):
+        """An OR of VICGPU_CELLERR_*: a cell whose flag word has one of these bits set after a step is skipped from the next
+        step on, decided on the device.  0 (the default): no cell is ever retired."""
+        self._chk(self.lib.vicgpu_set_retire_on_error(self.h, int(mask)))
+
+    def set_cell_valid(self, valid):
+        """[ncell]: 0 = skip the cell from the next step on (put_data_init included), non-zero = step it."""
+        v = np.ascontiguousarray(valid, dtype=np.int32)
+        assert v.shape == (self.dom.ncell,), v.shape
+        self._chk(self.lib.vicgpu_set_cell_valid(self.h, _i(v)))
+
+    def get_cell_valid(self):
+        v = np.zeros(self.dom.ncell, dtype=np.int32)
+        self._chk(self.lib.vicgpu_get_cell_valid(self.h, _i(v)))
+        return v
 
     def set_write_fluxes(self, on):
         self._chk(self.lib.vicgpu_set_write_fluxes(self.h, int(bool(on))))

@@ -22,12 +22,19 @@ struct GArgs {
   const int* hpi;
   double* sd;
   double* eq;          // [GMB_NROW][ncell]
+  const int* valid;    // [ncell] cell validity words (CELL_*, vic_types.hpp), or null: every cell is valid
 };
 
 __global__ __launch_bounds__(64) void vic_glacier_fit(const GArgs a) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= a.ncell) return;
   const size_t nh = a.nhru, nc = a.ncell;
+  if (a.valid && a.valid[c] != CELL_VALID) {
+    // vicNl.c:562 skips accumulateGlacierMassBalance for an invalid cell: the default equation, and no reset of its HRUs
+    a.eq[(size_t)GMB_B0 * nc + c] = 0; a.eq[(size_t)GMB_B1 * nc + c] = 0; a.eq[(size_t)GMB_B2 * nc + c] = 0;
+    a.eq[(size_t)GMB_FIT_ERROR * nc + c] = -1;
+    return;
+  }
   CellView cv{a.cell_params, a.ncell, c, a.o.Nnode, a.o.Nband};
   double X[VIC_MAX_BANDS], Y[VIC_MAX_BANDS];      // at most one point per band elevation
   int np = 0;
@@ -231,12 +238,23 @@ struct CArgs {
   double* cell_out;   // [CO_NROW][ncell]
   double* accum;      // [CA_NROW][ncell]
   int* cell_err;      // [ncell], OR-accumulated
+  int* valid;         // [ncell] cell validity words (CELL_*, vic_types.hpp), or null: every cell is valid
+  int retire_mask;    // VICGPU_CELLERR_* bits that retire a cell (vicgpu_set_retire_on_error)
 };
 
 __global__ __launch_bounds__(256) void vic_cell_reduce(const CArgs a) {
   const int ci = blockIdx.x * 256 + threadIdx.x;
   if (ci >= a.ccount) return;
   const int c = a.c0 + ci;
+  // an invalid cell keeps its sums, its step count and its flag word; the cell that took its last step in the step before
+  // (put_data has seen it since) is skipped from here on
+  if (a.valid) {
+    const int v = a.valid[c];
+    if (v != CELL_VALID) {
+      if (v == CELL_LAST) a.valid[c] = CELL_SKIP;
+      return;
+    }
+  }
   const size_t nh = a.nhru, nc = a.ncell;
   double op = 0, orn = 0, os = 0, ro = 0, bf = 0, ev = 0, swe = 0, sm0 = 0, sm1 = 0, sm2 = 0, gmb = 0;
   int err = 0;
@@ -272,7 +290,10 @@ __global__ __launch_bounds__(256) void vic_cell_reduce(const CArgs a) {
   a.accum[(size_t)CA_SOIL_MOIST_END2 * nc + c] = sm2;
   a.accum[(size_t)CA_GLAC_MASS_BALANCE * nc + c] += gmb;
   a.accum[(size_t)CA_NSTEPS * nc + c] += 1.0;
-  a.cell_err[c] |= err;
+  err |= a.cell_err[c];
+  a.cell_err[c] = err;
+  // vicNl.c:545-559: isValid = FALSE after a step that returned ERROR; this step's put_data still runs (dist_prec.c:167)
+  if (a.valid && (err & a.retire_mask)) a.valid[c] = CELL_LAST;
 }
 
 // ------------------------------------------------------------------------------------------------ state-file records

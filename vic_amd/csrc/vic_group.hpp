@@ -385,6 +385,24 @@ int vicgpu_group_get_cell_errors(vicgpu_group* g, int* flags) {
   return group_each(g, [&](int k) { return d2h_cols(g->ctx[k], flags + g->c0(k), g->ncell, g->ctx[k]->dom.d_cell_err, 1); });
 }
 
+// Cell validity (vicgpu.h): the mask is every shard's; shard k's part of the validity table is the caller's [c0(k), c0(k + 1))
+int vicgpu_group_set_retire_on_error(vicgpu_group* g, int mask) {
+  if (!g) return VICGPU_ERR_ARG;
+  return group_each(g, [&](int k) { return vicgpu_set_retire_on_error(g->ctx[k], mask); });
+}
+
+int vicgpu_group_set_cell_valid(vicgpu_group* g, const int* valid) {
+  if (!g || !valid) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return vicgpu_set_cell_valid(g->ctx[k], valid + g->c0(k)); });
+}
+
+int vicgpu_group_get_cell_valid(vicgpu_group* g, int* valid) {
+  if (!g || !valid) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return vicgpu_get_cell_valid(g->ctx[k], valid + g->c0(k)); });
+}
+
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset) {
   if (!g || !eq) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;

@@ -61,6 +61,7 @@ struct KArgs {
   int* lastexp;                     // IMPLICIT: [nhru] record slot holding the flags of the root find's last explicit solve
   int* jl;                          // QUICK_SOLVE: [nhru] end of the column the profile kernel solves
   int phase;                        // 0: start of the step; p >= 1: after the root finder of sub-step p - 1
+  const int* valid;                 // [ncell] cell validity words (CELL_*), or null: every cell is valid
 };
 
 // ------------------------------------------------------------------------------------------------ state table I/O

@@ -137,6 +137,9 @@ __global__ __launch_bounds__(64) void vic_hru_step(const KArgs a) {
   const int g = a.glist ? a.glist[gi] : gi;
   const Opt& o = a.o;
   const HruId id = hru_id(a, g);
+  // an invalid cell (vicNl.c:521): nothing of its HRUs is read or written, not even the zero record.  The lanes of a wave are
+  // consecutive cells of one slot: one coalesced int row; without a table the branch is wave-uniform
+  if (a.valid && a.valid[id.c] != CELL_VALID) return;
   // two instantiations share this body: GLAC = false handles ordinary HRUs (and writes the zero record of inactive
   // ones), GLAC = true handles glacier HRUs; the domain numbering keeps either kind wave-uniform
   if (id.is_glacier != GLAC && id.run) return;
@@ -199,6 +202,9 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
   const Opt& o = a.o;
   const HruId id = hru_id(a, g);
   if (id.run && id.is_glacier) return;              // vic_hru_step<NN, true> owns glacier HRUs
+  // an invalid cell (vicNl.c:521): its HRUs stay idle for the whole step -- no zero record, no work list, no round; the later
+  // phases and the evaluation kernel pass them by on hstate
+  if (FIRST && a.valid && a.valid[id.c] != CELL_VALID) { a.hstate[g] = 0; return; }
   if (FIRST && !id.run) { store_zero_record(a, g); a.hstate[g] = 0; return; }
   if (!FIRST && (a.hstate[g] & HS_STATE) != 2) return;
   CellView cv{a.cell_params, a.ncell, id.c, o.Nnode, o.Nband};

@@ -69,6 +69,11 @@ struct Domain {
   bool any_glacier = false;
   DevBuf<double> d_cp, d_hpd, d_sd, d_flux, d_cell_out, d_accum;
   DevBuf<int> d_hpi, d_si, d_cell_off, d_cell_list, d_hru_err, d_cell_err;
+  // cell validity (vicgpu_set_cell_valid, vicgpu_set_retire_on_error): the words CELL_* of vic_types.hpp, all CELL_VALID after
+  // vicgpu_set_domain.  valid_live: a word may differ from CELL_VALID -- the host has marked a cell invalid, or steps have run
+  // with a retire mask; until then the kernels get a null table (valid_table) and take no load for it
+  DevBuf<int> d_valid;
+  bool valid_live = false;
   // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
   bool fd = false;
   DevBuf<unsigned long long> d_ctx;
@@ -194,7 +199,11 @@ struct vicgpu_ctx {
   int profile_waves = 0;           // resident waves of the profile kernel
   int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
   int out_step_ratio = 1;
+  int retire_mask = 0;             // vicgpu_set_retire_on_error; a setting of the context, not of the domain
 };
+
+// the validity table as the kernels take it: null while every cell is known to be valid
+static int* valid_table(const vicgpu_ctx* c) { return c->dom.valid_live ? c->dom.d_valid.get() : nullptr; }
 
 // the stream that carries the output records to the host (see Records)
 static hipStream_t records_stream(const vicgpu_ctx* c) { return c->rec.dl ? (hipStream_t)c->rec.dl : (hipStream_t)c->stream; }
@@ -309,6 +318,7 @@ static KArgs make_kargs(const vicgpu_ctx* c) {
   ka.veglib = c->d_veglib; ka.cell_params = d.d_cp; ka.hpi = d.d_hpi; ka.hpd = d.d_hpd; ka.sd = d.d_sd; ka.si = d.d_si; ka.flux = d.d_flux;
   ka.hru_err = d.d_hru_err; ka.ctx = d.d_ctx; ka.pin = d.d_pin; ka.ts = d.d_ts; ka.pout = d.d_pout; ka.pslot = d.d_pslot;
   ka.hstate = d.d_hstate; ka.hkey = d.d_hkey; ka.pimp = d.d_pimp; ka.lastexp = d.d_lastexp; ka.jl = d.d_jl;
+  ka.valid = valid_table(c);
   return ka;
 }
 static CArgs make_cargs(const vicgpu_ctx* c) {
@@ -317,6 +327,7 @@ static CArgs make_cargs(const vicgpu_ctx* c) {
   ca.ncell = d.ncell; ca.nhru = d.nhru; ca.ccount = d.ncell; ca.cell_off = d.d_cell_off; ca.cell_list = d.d_cell_list; ca.hpd = d.d_hpd;
   ca.hpi_glac = d.d_hpi + (size_t)HPI_IS_GLACIER * d.nhru; ca.flux = d.d_flux; ca.sd = d.d_sd; ca.hru_err = d.d_hru_err;
   ca.cell_out = d.d_cell_out; ca.accum = d.d_accum; ca.cell_err = d.d_cell_err;
+  ca.valid = valid_table(c); ca.retire_mask = c->retire_mask;
   return ca;
 }
 static PArgs profile_args(const vicgpu_ctx* c, const FdChunk* ch) {
@@ -440,6 +451,7 @@ static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, i
   a.hpi = c->dom.d_hpi; a.hpd = c->dom.d_hpd; a.sd = c->dom.d_sd; a.si = c->dom.d_si; a.flux = c->dom.d_flux;
   a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->dom.ncell;
   a.cell_out = c->dom.d_cell_out; a.out_data = c->dom.d_out_data; a.out_agg = c->dom.d_out_agg; a.pb = c->dom.d_pb;
+  a.valid = valid_table(c);
   const unsigned nblk = (unsigned)((ccount + 63) / 64);
   // zero_output_list: the columns of these cells in every row
   hipLaunchKernelGGL(vic_put_zero, dim3(nblk, (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
@@ -566,6 +578,9 @@ static int domain_tables(vicgpu_ctx* c, const double* cell_params, const int* hp
   HIPCHK(c, d.d_accum.alloc_fill(CA_NROW * ncell, 0, st));
   HIPCHK(c, d.d_hru_err.alloc_fill(nhru, 0, st));
   HIPCHK(c, d.d_cell_err.alloc_fill(ncell, 0, st));
+  const std::vector<int> all_valid(ncell, CELL_VALID);
+  HIPCHK(c, d.d_valid.alloc(ncell));
+  HIPCHK(c, d.d_valid.upload(st, all_valid.data()));
   return VICGPU_OK;
 }
 

@@ -65,7 +65,17 @@ struct OArgs {
   double* out_data;             // [nrow][ncell]
   double* out_agg;              // [nrow][ncell]
   double* pb;                   // [PBX_NROW][ncell]: the public rows + this file's own
+  const int* valid;             // [ncell] cell validity words (CELL_*, vic_types.hpp), or null: every cell is valid
 };
+
+// vicNl.c:521 precedes put_data: every kernel of this file leaves the rows of a skipped cell alone -- its output values, its
+// aggregates and its bookkeeping.  A cell that has just taken its last step still gets that step's put_data (dist_prec.c:167),
+// but no initialisation call.
+VIC_DEV bool put_skips(const OArgs& a, int c) {
+  if (!a.valid) return false;
+  const int v = a.valid[c];
+  return v == CELL_SKIP || (a.rec < 0 && v != CELL_VALID);
+}
 
 // rows this file appends to the bookkeeping table: the partial areas of put_data.c:262-300
 enum { PBX_CV_BARESOIL = PB_NROW, PBX_CV_VEG, PBX_CV_OVERSTORY, PBX_CV_SNOW, PBX_CV_GLACIER, PBX_NROW };
@@ -406,6 +416,7 @@ VIC_DEV void put_sum(const OArgs& a) {
   const int ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= a.ccount) return;
   const int c = a.c0 + ci;
+  if (put_skips(a, c)) return;
   if (blockIdx.y == 0) put_sum_part<0, DEEP>(a, c);
   else if (blockIdx.y == 1) put_sum_part<1, DEEP>(a, c);
   else put_sum_part<2, DEEP>(a, c);
@@ -417,6 +428,7 @@ __global__ __launch_bounds__(64) void vic_put_finish(const OArgs a) {
   const int ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= a.ccount) return;
   const int c = a.c0 + ci;
+  if (put_skips(a, c)) return;
   const size_t nc = a.ncell;
   const Opt& o = a.o;
   const int NR = o.NR, ns = NR + 1;
@@ -536,6 +548,7 @@ __global__ __launch_bounds__(64) void vic_put_finish(const OArgs a) {
 __global__ __launch_bounds__(64) void vic_put_zero(const OArgs a) {
   const int ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= a.ccount) return;
+  if (put_skips(a, a.c0 + ci)) return;
   const size_t nc = a.ncell;
   const int nrow = a.lay.off[VOUT_NVAR];
   double* __restrict__ od = a.out_data + a.c0 + ci;
@@ -550,6 +563,7 @@ __global__ __launch_bounds__(64) void vic_put_aggregate(const OArgs a, const uns
   const int ci = blockIdx.x * 64 + threadIdx.x;
   if (ci >= a.ccount) return;
   const int c = a.c0 + ci;
+  if (put_skips(a, c)) return;
   const size_t nc = a.ncell;
   const int nrow = a.lay.off[VOUT_NVAR];
   const int r0 = blockIdx.y * PUT_AGG_ROWS;

@@ -121,6 +121,15 @@ struct Opt {
   double wind_h;
 };
 
+// ---- cell validity (vicgpu_set_retire_on_error / vicgpu_set_cell_valid): one word per cell next to the flag word ----
+//   CELL_VALID  the step computes the cell
+//   CELL_LAST   the cell was stepped for the last time: vic_cell_reduce of the failing step writes it, so that the put_data
+//               kernels behind it still see the cell (dist_prec.c:167); the next vic_cell_reduce turns it into CELL_SKIP
+//   CELL_SKIP   nothing touches the cell
+// The HRU kernels and the calls between steps (put_data initialisation, glacier fit) work on CELL_VALID cells only; the
+// cell-level kernels of a step leave CELL_SKIP cells alone.  A null table means that every cell is valid.
+enum { CELL_SKIP = 0, CELL_VALID = 1, CELL_LAST = 2 };
+
 // ---- read-only views ----
 struct VegLib {
   const double* __restrict__ t;   // [nrow][VL_NFIELD]

@@ -316,6 +316,7 @@ static int step_impl(vicgpu_ctx* c, int step0, int nsteps, int ratio) {
   c->ev_steps = 0;
   StepPlan plan;
   plan.c = c; plan.step0 = step0; plan.nsteps = nsteps; plan.records = records; plan.ratio = ratio;
+  if (c->retire_mask) c->dom.valid_live = true;      // these steps may retire cells: the kernels take the validity table from here on
   plan.ka = make_kargs(c); plan.ca = make_cargs(c);
   KArgs& ka = plan.ka;
   const CArgs& ca = plan.ca;
@@ -411,6 +412,39 @@ int vicgpu_reset_accum(vicgpu_ctx* c) {
   return VICGPU_OK;
 }
 
+// ---- cell validity: cell.isValid and CONTINUEONERROR (vicNl.c:429, 521, 545-559)
+int vicgpu_set_retire_on_error(vicgpu_ctx* c, int mask) {
+  const int all = VICGPU_CELLERR_SOLVER | VICGPU_CELLERR_AERO | VICGPU_CELLERR_NODES | VICGPU_CELLERR_NAN;
+  if (!c || (mask & ~all)) return VICGPU_ERR_ARG;
+  c->retire_mask = mask;           // read when the next steps are queued; the table keeps what earlier steps left in it
+  return VICGPU_OK;
+}
+
+int vicgpu_set_cell_valid(vicgpu_ctx* c, const int* valid) {
+  if (!c || !valid) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the steps queued so far ran on the table as it was
+  std::vector<int> w(c->dom.ncell);
+  bool any_invalid = false;
+  for (size_t i = 0; i < w.size(); i++) {
+    w[i] = valid[i] ? CELL_VALID : CELL_SKIP;
+    any_invalid = any_invalid || !valid[i];
+  }
+  HIPCHK(c, c->dom.d_valid.upload(c->stream, w.data()));
+  c->dom.valid_live = any_invalid;
+  return VICGPU_OK;
+}
+
+int vicgpu_get_cell_valid(vicgpu_ctx* c, int* valid) {
+  if (!c || !valid) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  const int r = d2h(c, valid, c->dom.d_valid);
+  if (r != VICGPU_OK) return r;
+  for (int i = 0; i < c->dom.ncell; i++) valid[i] = valid[i] == CELL_VALID ? 1 : 0;
+  return VICGPU_OK;
+}
+
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld) {
   if (!c || !c->dom.d_cp || !eq || ld < c->dom.ncell) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
@@ -419,6 +453,7 @@ static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld) {
   GArgs g;
   g.o = c->o; g.ncell = c->dom.ncell; g.nhru = c->dom.nhru; g.reset = reset ? 1 : 0; g.cell_params = c->dom.d_cp; g.cell_off = c->dom.d_cell_off;
   g.cell_list = c->dom.d_cell_list; g.hpi = c->dom.d_hpi; g.sd = c->dom.d_sd; g.eq = d_eq;
+  g.valid = valid_table(c);
   hipLaunchKernelGGL(vic_glacier_fit, dim3((c->dom.ncell + 63) / 64), dim3(64), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
