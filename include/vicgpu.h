@@ -136,7 +136,8 @@ enum {
  * atmos_data_struct (vicNl_def.h:1060-1076).  Units as inside the reference's
  * time loop: T in C, prec mm/step, pressure/vp/vpd in Pa, W/m2, kg/m3, m/s.
  * Layout double[nsteps][VIC_NFORCE][NF+1][ncell]; sub-index NR holds the
- * step average, 0..NF-1 the snow sub-steps.  snowflag uint8[nsteps][NF+1][ncell]. */
+ * step average, 0..NF-1 the snow sub-steps.  snowflag uint8[nsteps][NF+1][ncell].  With a forcing map
+ * (vicgpu_set_forcing_map) the forcing and raw tables are ncol wide, the flags stay ncell wide. */
 enum {
   VIC_F_AIR_TEMP = 0, VIC_F_PREC, VIC_F_PRESSURE, VIC_F_VP, VIC_F_VPD,
   VIC_F_DENSITY, VIC_F_SHORTWAVE, VIC_F_LONGWAVE, VIC_F_WIND, VIC_NFORCE
@@ -385,6 +386,32 @@ int vicgpu_get_forcing(vicgpu_ctx *ctx, int step, double *forcing /* [VIC_NFORCE
                        unsigned char *snowflag /* [NF+1][ncell] */);       /* read-back of the current chunk (tests) */
 void *vicgpu_host_alloc(size_t bytes);                  /* pinned host memory for forcing chunks */
 void vicgpu_host_free(void *p);
+
+/* ---- forcing map: cells that share forcing columns (ensembles over the same meteorology -- calibration, sensitivity and
+ * perturbed-state runs, whose members are just more cells -- and a model grid finer than its forcing grid).
+ *   vicgpu_set_forcing_map   cell_col[ncell], 0 <= cell_col[c] < ncol, ncol >= 1: cell c reads forcing column cell_col[c].  A
+ *                            column may be used by any number of cells or by none; any map is legal (it need not be monotone
+ *                            or blocked).  cell_col == NULL (with ncol 0 or ncell): the identity, every cell its own column.
+ *   vicgpu_get_forcing_map   *ncol, and the map into cell_col[ncell] unless cell_col is NULL.
+ * Once a map is set every forcing table is ncol wide instead of ncell wide: forcing of vicgpu_push_forcing /
+ * vicgpu_prefetch_forcing and of vicgpu_get_forcing is [nsteps][VIC_NFORCE][NF+1][ncol], raw of vicgpu_prefetch_forcing_raw is
+ * [nsteps][VIC_NRAW][dt][ncol], and VICGPU_PTR_FORCING points to the current chunk in that layout.  put_data's forcing echoes
+ * (OUT_AIR_TEMP .. OUT_WIND, OUT_QAIR, OUT_REL_HUMID; OUT_PREC / OUT_RAINF / OUT_SNOWF come from the cell's own step) are those
+ * of the cell's column.
+ * snowflag stays per cell, [nsteps][NF+1][ncell]: the flag is a function of the cell's own parameters (the smallest Tfactor
+ * of its bands, MAX_SNOW_TEMP, MIN_RAIN_TEMP: initialize_atmos.c:1275-1303) -- calibration parameters, so two members on one
+ * column may differ in it.  vicgpu_prefetch_forcing_raw derives the nine numeric rows once per column (they depend on the raw
+ * values and the options only) and the flag once per cell, from that cell's parameters and its column's air temperature and
+ * precipitation.
+ * The map belongs to the domain: vicgpu_set_domain resets it to the identity.  Setting a map (the identity included) waits
+ * for the steps queued so far and drops both forcing chunks, because a chunk's rows are as wide as the map it was pushed for:
+ * vicgpu_step and vicgpu_run_records return VICGPU_ERR_STATE until a chunk is pushed, as after vicgpu_set_domain.  The state,
+ * the validity table, the put_data and records configuration and the aggregates are untouched.
+ * VICGPU_ERR_ARG: a null handle (or ncol pointer), ncol < 1 with a map, an entry outside [0, ncol), NULL with an ncol other
+ * than 0 or ncell -- the map and the chunk in force stay; VICGPU_ERR_STATE: no domain; VICGPU_ERR_HIP: the runtime refused an
+ * allocation -- nothing is left behind and the map in force stays. */
+int vicgpu_set_forcing_map(vicgpu_ctx *ctx, int ncol, const int *cell_col);
+int vicgpu_get_forcing_map(vicgpu_ctx *ctx, int *ncol, int *cell_col);   /* cell_col may be NULL: ncol only */
 
 /* ---- the hot path: for rec in [step0, step0+nsteps): dist_prec for every cell
  * (vicNl.c:506-543).  With QUICK_FLUX the call only enqueues work.  With the

@@ -67,6 +67,12 @@ int vicgpu_group_prefetch_forcing(vicgpu_group *g, int nsteps, const double *for
 int vicgpu_group_prefetch_forcing_raw(vicgpu_group *g, int nsteps, const double *raw, const int *dmy, double min_wind_speed,
                                       int plapse);
 int vicgpu_group_swap_forcing(vicgpu_group *g);
+/* forcing map (vicgpu.h): cell_col[ncell] in the caller's global cell order, the forcing and raw tables of the entries above
+ * then ncol wide, the flags ncell wide.  Shard k takes the column range [lo_k, hi_k] its cells span, with its own map rebased
+ * by lo_k: its uploads are the same pitched copies, leading dimension ncol, from column lo_k, hi_k - lo_k + 1 wide.
+ * vicgpu_group_set_domain resets the map to the identity; so does a call that fails in a shard (VICGPU_ERR_HIP). */
+int vicgpu_group_set_forcing_map(vicgpu_group *g, int ncol, const int *cell_col);
+int vicgpu_group_get_forcing_map(vicgpu_group *g, int *ncol, int *cell_col);   /* cell_col may be NULL: ncol only */
 int vicgpu_group_step(vicgpu_group *g, int step0, int nsteps);
 int vicgpu_group_synchronize(vicgpu_group *g);
 int vicgpu_group_put_data_config(vicgpu_group *g, int out_step_ratio);

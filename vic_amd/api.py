@@ -72,6 +72,8 @@ def load_library():
         "vicgpu_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
         "vicgpu_swap_forcing": (ctypes.c_int, [vp]),
         "vicgpu_get_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up]),
+        "vicgpu_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
+        "vicgpu_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -110,6 +112,8 @@ def load_library():
         "vicgpu_group_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_group_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
         "vicgpu_group_swap_forcing": (ctypes.c_int, [vp]),
+        "vicgpu_group_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
+        "vicgpu_group_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
         "vicgpu_group_step": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "vicgpu_group_synchronize": (ctypes.c_int, [vp]),
         "vicgpu_group_put_data_config": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -144,6 +148,7 @@ GROUP_ENTRIES = [
     "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
     "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
+    "set_forcing_map", "get_forcing_map",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -158,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_records_config", "vicgpu_records_nrow", "vicgpu_run_records", "vicgpu_records_wait",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
+    "vicgpu_set_forcing_map", "vicgpu_get_forcing_map",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -228,6 +234,7 @@ class Model:
         self._chk(self.lib.vicgpu_set_domain(self.h, dom.ncell, dom.nhru, _d(dom.cell_params), _i(dom.hru_iparams),
                                              _d(dom.hru_dparams), _i(dom.cell_hru_offset), _i(dom.cell_hru_list)))
         self.dom = dom
+        self.ncol = dom.ncell        # the forcing map of a fresh domain is the identity
 
     def _chk(self, rc):
         if rc != 0:
@@ -268,7 +275,7 @@ class Model:
         snowflag = np.ascontiguousarray(snowflag, dtype=np.uint8)
         dmy = np.ascontiguousarray(dmy, dtype=np.int32)
         n = forcing.shape[0]
-        assert forcing.shape == (n, C["VIC_NFORCE"], self.opt.NR + 1, self.dom.ncell), forcing.shape
+        assert forcing.shape == (n, C["VIC_NFORCE"], self.opt.NR + 1, self.ncol), forcing.shape
         assert snowflag.shape == (n, self.opt.NR + 1, self.dom.ncell)
         assert dmy.shape == (n, C["VIC_NDMY"])
         self._hold = (forcing, snowflag, dmy)   # the H2D copy is asynchronous
@@ -280,7 +287,7 @@ class Model:
         snowflag = np.ascontiguousarray(snowflag, dtype=np.uint8)
         dmy = np.ascontiguousarray(dmy, dtype=np.int32)
         n = forcing.shape[0]
-        assert forcing.shape == (n, C["VIC_NFORCE"], self.opt.NR + 1, self.dom.ncell), forcing.shape
+        assert forcing.shape == (n, C["VIC_NFORCE"], self.opt.NR + 1, self.ncol), forcing.shape
         assert snowflag.shape == (n, self.opt.NR + 1, self.dom.ncell)
         self._hold_next = (forcing, snowflag, dmy)   # pinned sources are read until swap_forcing returns
         self._chk(self.lib.vicgpu_prefetch_forcing(self.h, n, _d(forcing), snowflag.ctypes.data_as(_up), _i(dmy)))
@@ -290,7 +297,7 @@ class Model:
         raw = np.ascontiguousarray(raw, dtype=np.float64)
         dmy = np.ascontiguousarray(dmy, dtype=np.int32)
         n = raw.shape[0]
-        assert raw.shape == (n, C["VIC_NRAW"], self.opt.dt, self.dom.ncell), raw.shape
+        assert raw.shape == (n, C["VIC_NRAW"], self.opt.dt, self.ncol), raw.shape
         self._hold_next = (raw, dmy)
         self._chk(self.lib.vicgpu_prefetch_forcing_raw(self.h, n, _d(raw), _i(dmy), float(min_wind_speed), int(bool(plapse))))
 
@@ -298,8 +305,30 @@ class Model:
         self._chk(self.lib.vicgpu_swap_forcing(self.h))
         self._hold = getattr(self, "_hold_next", None)
 
+    # ---- forcing map: cells that share forcing columns (ensembles, a model grid finer than its forcing grid)
+    def set_forcing_map(self, cell_col, ncol=None):
+        """vicgpu_set_forcing_map: cell c reads forcing column cell_col[c] of the ncol-wide forcing and raw tables (ncol None:
+        max(cell_col) + 1); the snowflag stays [..][ncell].  cell_col None: every cell its own column again.  Drops the forcing
+        chunks: push one before the next step."""
+        if cell_col is None:
+            self._chk(self.lib.vicgpu_set_forcing_map(self.h, 0, None))
+            self.ncol = self.dom.ncell
+            return
+        m = np.ascontiguousarray(cell_col, dtype=np.int32)
+        assert m.shape == (self.dom.ncell,), m.shape
+        ncol = int(m.max()) + 1 if ncol is None else int(ncol)
+        self._chk(self.lib.vicgpu_set_forcing_map(self.h, ncol, _i(m)))
+        self.ncol = ncol
+
+    def get_forcing_map(self):
+        """(ncol, cell_col [ncell]) as the library holds it."""
+        n = ctypes.c_int(0)
+        m = np.zeros(self.dom.ncell, dtype=np.int32)
+        self._chk(self.lib.vicgpu_get_forcing_map(self.h, ctypes.byref(n), _i(m)))
+        return n.value, m
+
     def get_forcing(self, step):
-        f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.dom.ncell)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)
+        f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)
         self._chk(self.lib.vicgpu_get_forcing(self.h, int(step), _d(f), sf.ctypes.data_as(_up)))
         return f, sf
 

@@ -350,36 +350,49 @@ __global__ __launch_bounds__(256) void vic_state_records(const RArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ forcing derivation
-// initialize_atmos.c, the derivation of atmos[rec] from the hourly forcing of one record (see include/vicgpu.h): one lane
-// per (step, cell)
+// initialize_atmos.c, the derivation of atmos[rec] from the hourly forcing of one record (see include/vicgpu.h).  The nine
+// numeric rows depend on the raw values and the options only, the snowflag on the cell's parameters too (:1275-1303: the
+// coldest band's Tfactor, MAX_SNOW_TEMP, MIN_RAIN_TEMP).  Without a forcing map a lane is one (step, cell) and does both.
+// With one (vicgpu_set_forcing_map) the rows are derived once per (step, column) and the flags once per (step, cell), by the
+// same expression from the column's T and prec, re-read from the derived table.
 struct FArgs {
   int nsteps, ncell, dt, snow_step, NF, NR, temp_th_type, Nband, Nnode, plapse;
+  int ncol;                    // columns of raw and forcing; ncell without a map
   double min_wind;
   const double* raw;
   const double* cell_params;
   double* forcing;
   unsigned char* snowflag;
+  const int* cell_col;         // [ncell], read by vic_derive_forcing_flags only
 };
 
-extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing(const FArgs a) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)a.nsteps * a.ncell) return;
-  const int s = (int)(i / a.ncell), c = (int)(i % a.ncell);
-  const size_t nc = a.ncell;
+// step s: the rows of column col (VALUES) and / or the flags of cell c, whose column is col (FLAGS)
+template <bool VALUES, bool FLAGS>
+VIC_DEV void derive_forcing_lane(const FArgs& a, int s, int col, int c) {
+  const size_t nc = a.ncell, nw = a.ncol;
   const int ns = a.NR + 1, NF = a.NF;
-  const double* raw = a.raw + (size_t)s * VIC_NRAW * a.dt * nc + c;
-  double* f = a.forcing + (size_t)s * VIC_NFORCE * ns * nc + c;
+  const double* raw = a.raw + (size_t)s * VIC_NRAW * a.dt * nw + col;
+  double* f = a.forcing + (size_t)s * VIC_NFORCE * ns * nw + col;
   unsigned char* sf = a.snowflag + (size_t)s * ns * nc + c;
-#define RAW(v, h) raw[((size_t)(v) * a.dt + (h)) * nc]
-#define F(v, j) f[((size_t)(v) * ns + (j)) * nc]
-  CellView cv{a.cell_params, a.ncell, c, a.Nnode, a.Nband};
-  double min_Tfactor = cv.band(CPB_TFACTOR, 0);                                       // initialize_atmos.c:1275-1280
-  for (int b = 1; b < a.Nband; b++) { const double t = cv.band(CPB_TFACTOR, b); if (t < min_Tfactor) min_Tfactor = t; }
-  const double max_snow = cv.s(CP_MAX_SNOW_TEMP), min_rain = cv.s(CP_MIN_RAIN_TEMP);
-  const double thr = (a.temp_th_type == VIC_TEMP_TH_KIENZLE) ? (max_snow + min_rain / 2) : max_snow;
+#define RAW(v, h) raw[((size_t)(v) * a.dt + (h)) * nw]
+#define F(v, j) f[((size_t)(v) * ns + (j)) * nw]
+  double min_Tfactor = 0, thr = 0;
+  if constexpr (FLAGS) {
+    CellView cv{a.cell_params, a.ncell, c, a.Nnode, a.Nband};
+    min_Tfactor = cv.band(CPB_TFACTOR, 0);                                            // initialize_atmos.c:1275-1280
+    for (int b = 1; b < a.Nband; b++) { const double t = cv.band(CPB_TFACTOR, b); if (t < min_Tfactor) min_Tfactor = t; }
+    const double max_snow = cv.s(CP_MAX_SNOW_TEMP), min_rain = cv.s(CP_MIN_RAIN_TEMP);
+    thr = (a.temp_th_type == VIC_TEMP_TH_KIENZLE) ? (max_snow + min_rain / 2) : max_snow;
+  }
   double sT = 0, sP = 0, sPr = 0, sVp = 0, sVpd = 0, sD = 0, sSw = 0, sLw = 0, sW = 0;
   bool any_snow = false;
   for (int j = 0; j < NF; j++) {
+    if constexpr (!VALUES) {                                                          // the flags of a mapped run: T and prec as derived
+      const bool snow = ((F(VIC_F_AIR_TEMP, j) + min_Tfactor) < thr) && (F(VIC_F_PREC, j) > 0);
+      sf[(size_t)j * nc] = snow ? 1 : 0;
+      any_snow = any_snow || snow;
+      continue;
+    }
     double T = 0, prec = 0, pr = 0, vp = 0, sw = 0, lw = 0, wind = 0;
     for (int h = j * a.snow_step; h < (j + 1) * a.snow_step; h++) {                   // the snow_step-hour aggregation (:886-893 et al.)
       T += RAW(VIC_RAW_AIR_TEMP, h); prec += RAW(VIC_RAW_PREC, h);
@@ -394,22 +407,51 @@ extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing(const FArgs
     if (vpd < 0) { vpd = 0; vp = svp(T); }
     F(VIC_F_AIR_TEMP, j) = T; F(VIC_F_PREC, j) = prec; F(VIC_F_PRESSURE, j) = pr; F(VIC_F_VP, j) = vp; F(VIC_F_VPD, j) = vpd;
     F(VIC_F_DENSITY, j) = dens; F(VIC_F_SHORTWAVE, j) = sw; F(VIC_F_LONGWAVE, j) = lw; F(VIC_F_WIND, j) = wind;
-    const bool snow = ((T + min_Tfactor) < thr) && (prec > 0);                        // :1283-1300
-    sf[(size_t)j * nc] = snow ? 1 : 0;
-    any_snow = any_snow || snow;
+    if constexpr (FLAGS) {
+      const bool snow = ((T + min_Tfactor) < thr) && (prec > 0);                      // :1283-1300
+      sf[(size_t)j * nc] = snow ? 1 : 0;
+      any_snow = any_snow || snow;
+    }
     sT += T; sP += prec; sPr += pr; sVp += vp; sVpd += vpd; sD += dens; sSw += sw; sLw += lw; sW += wind;
   }
-  if (NF > 1) {                                                                       // x[NR] = sum / (float)NF; prec[NR] = sum
+  if (NF > 1 && FLAGS) sf[(size_t)a.NR * nc] = any_snow ? 1 : 0;
+  if (NF > 1 && VALUES) {                                                             // x[NR] = sum / (float)NF; prec[NR] = sum
     const double n = (double)(float)NF;
     F(VIC_F_AIR_TEMP, a.NR) = sT / n; F(VIC_F_PREC, a.NR) = sP; F(VIC_F_PRESSURE, a.NR) = sPr / n; F(VIC_F_VP, a.NR) = sVp / n;
     F(VIC_F_VPD, a.NR) = sVpd / n; F(VIC_F_SHORTWAVE, a.NR) = sSw / n; F(VIC_F_LONGWAVE, a.NR) = sLw / n;
     F(VIC_F_WIND, a.NR) = sW / n;
     // density[NR] is derived from pressure[NR] and air_temp[NR] like every other slot (initialize_atmos.c:984-998), not averaged
     F(VIC_F_DENSITY, a.NR) = a.plapse ? (sPr / n) / (287.0 * (KELVIN + sT / n)) : 0.003486 * (sPr / n) / (275.0 + sT / n);
-    sf[(size_t)a.NR * nc] = any_snow ? 1 : 0;
   }
 #undef RAW
 #undef F
+}
+
+// no map: one lane per (step, cell), rows and flag
+extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing(const FArgs a) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)a.nsteps * a.ncell) return;
+  const int s = (int)(i / a.ncell), c = (int)(i % a.ncell);
+  derive_forcing_lane<true, true>(a, s, c, c);
+}
+// with a map: one lane per (step, column) for the rows, then one lane per (step, cell) for the flags
+extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing_cols(const FArgs a) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)a.nsteps * a.ncol) return;
+  derive_forcing_lane<true, false>(a, (int)(i / a.ncol), (int)(i % a.ncol), 0);
+}
+extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing_flags(const FArgs a) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)a.nsteps * a.ncell) return;
+  const int c = (int)(i % a.ncell);
+  derive_forcing_lane<false, true>(a, (int)(i / a.ncell), a.cell_col[c], c);
+}
+
+// the derived row of vicgpu_set_forcing_map: every HRU's forcing column, read by the step kernels next to the HPI rows
+extern "C" __global__ __launch_bounds__(256) void vic_fill_hru_fcol(const int* __restrict__ hpi_cell, const int* __restrict__ cell_col, int nhru,
+                                                          int* __restrict__ fcol) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g < nhru) fcol[g] = cell_col[hpi_cell[g]];
 }
 
 // ------------------------------------------------------------------------------------------------ output read-back

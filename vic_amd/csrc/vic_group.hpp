@@ -16,7 +16,7 @@
 
 // static helpers of vicgpu_api.hip with a pitch (ld: cells per row of the caller's table)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
-                         const int* dmy, double min_wind, int plapse, int ld);
+                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag);
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
 static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld);
@@ -86,8 +86,13 @@ struct vicgpu_group {
   std::vector<std::vector<int>> hru;        // shard k's HRUs: global id of its HRU j
   std::vector<int> rec_first;               // [nshard]: index of shard k's first state record = cell_hru_offset[bounds[k]]
   std::vector<int> rec_band, rec_veg;       // band and vegetation class of every state record (cell-major hruList order)
+  // forcing map (vicgpu_group_set_forcing_map), in the caller's global cell order: shard k holds the columns from col_lo[k]
+  // on that its cells span, its own map rebased by col_lo[k].  Identity: ncol == ncell, cell_col empty, col_lo[k] == bounds[k]
+  int ncol = 0;
+  std::vector<int> cell_col, col_lo;
   int nshard() const { return (int)ctx.size(); }
   int c0(int k) const { return bounds[k]; }
+  void identity_map() { ncol = ncell; cell_col.clear(); col_lo.assign(bounds.begin(), bounds.end() - 1); }
 };
 
 // fn(k) -> status on every shard at the same time; the first failing shard's code and message
@@ -262,7 +267,55 @@ int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* 
   }
   g->rec_first.resize(ns);
   for (int k = 0; k < ns; k++) g->rec_first[k] = off[b[k]];
+  g->identity_map();               // as every shard's vicgpu_set_domain has left it
   g->domain_ready = true;
+  return VICGPU_OK;
+}
+
+// Forcing map (vicgpu.h) in the caller's global cell order.  Shard k takes the column range [lo_k, hi_k] its cells span and
+// the map rebased by lo_k; the forcing and raw uploads below then start at column lo_k of the caller's ncol-wide tables.
+int vicgpu_group_set_forcing_map(vicgpu_group* g, int ncol, const int* cell_col) {
+  if (!g) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  if (!cell_col) {
+    if (ncol != 0 && ncol != g->ncell) return group_fail(g, VICGPU_ERR_ARG, "set_forcing_map: no map, but ncol is neither 0 nor ncell");
+    const int r = group_each(g, [&](int k) { return vicgpu_set_forcing_map(g->ctx[k], 0, nullptr); });
+    if (r == VICGPU_OK) g->identity_map();
+    return r;
+  }
+  if (ncol < 1) return group_fail(g, VICGPU_ERR_ARG, "set_forcing_map: ncol < 1");
+  for (int i = 0; i < g->ncell; i++)
+    if (cell_col[i] < 0 || cell_col[i] >= ncol) return group_fail(g, VICGPU_ERR_ARG, "set_forcing_map: entry " + std::to_string(i) + " is not a column");
+  const int ns = g->nshard();
+  std::vector<int> lo(ns), width(ns);
+  for (int k = 0; k < ns; k++) {
+    const int* first = cell_col + g->bounds[k];
+    const int* last = cell_col + g->bounds[k + 1];
+    lo[k] = *std::min_element(first, last);
+    width[k] = *std::max_element(first, last) - lo[k] + 1;
+  }
+  const int r = group_each(g, [&](int k) {
+    std::vector<int> local(cell_col + g->bounds[k], cell_col + g->bounds[k + 1]);
+    for (int& v : local) v -= lo[k];
+    return vicgpu_set_forcing_map(g->ctx[k], width[k], local.data());
+  });
+  if (r != VICGPU_OK) {            // a shard's allocation was refused: no shard keeps a map the others do not have
+    std::string msg = g->err;
+    group_each(g, [&](int k) { return vicgpu_set_forcing_map(g->ctx[k], 0, nullptr); });
+    g->identity_map();
+    g->err = msg + " (the group is back on the identity map)";
+    return r;
+  }
+  g->ncol = ncol; g->cell_col.assign(cell_col, cell_col + g->ncell); g->col_lo = lo;
+  return VICGPU_OK;
+}
+
+int vicgpu_group_get_forcing_map(vicgpu_group* g, int* ncol, int* cell_col) {
+  if (!g || !ncol) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  *ncol = g->ncol;
+  if (cell_col)
+    for (int i = 0; i < g->ncell; i++) cell_col[i] = g->cell_col.empty() ? i : g->cell_col[i];
   return VICGPU_OK;
 }
 
@@ -319,7 +372,7 @@ int vicgpu_group_prefetch_forcing(vicgpu_group* g, int nsteps, const double* for
   if (!g || !forcing || !snowflag || !dmy) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) {
-    return prefetch_impl(g->ctx[k], nsteps, forcing + g->c0(k), snowflag + g->c0(k), nullptr, dmy, 0.0, 1, g->ncell);
+    return prefetch_impl(g->ctx[k], nsteps, forcing + g->col_lo[k], snowflag + g->c0(k), nullptr, dmy, 0.0, 1, g->ncol, g->ncell);
   });
 }
 
@@ -327,7 +380,7 @@ int vicgpu_group_prefetch_forcing_raw(vicgpu_group* g, int nsteps, const double*
   if (!g || !raw || !dmy) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) {
-    return prefetch_impl(g->ctx[k], nsteps, nullptr, nullptr, raw + g->c0(k), dmy, min_wind_speed, plapse, g->ncell);
+    return prefetch_impl(g->ctx[k], nsteps, nullptr, nullptr, raw + g->col_lo[k], dmy, min_wind_speed, plapse, g->ncol, g->ncell);
   });
 }
 

@@ -37,8 +37,10 @@ struct KArgs {
   const double* cell_params;
   const int* hpi;
   const double* hpd;
-  const double* forcing;            // this step: [VIC_NFORCE][NF+1][ncell]
+  const double* forcing;            // this step: [VIC_NFORCE][NF+1][ncol]
   const unsigned char* snowflag;    // this step: [NF+1][ncell]
+  const int* fcol;                  // [nhru] forcing column of each HRU's cell; without a map the HPI_CELL row itself
+  int ncol;                         // forcing columns (vicgpu_set_forcing_map); ncell without a map
   Dmy dmy;
   double* sd;
   int* si;

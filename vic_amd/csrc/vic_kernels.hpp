@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64) void vic_hru_step(const KArgs a) {
   PROF_T0(t_kernel);
   CellView cv{a.cell_params, a.ncell, id.c, o.Nnode, o.Nband};
   VegLib vl{a.veglib};
-  Forcing fc{a.forcing, a.snowflag, a.ncell, id.c, o.NR + 1};
+  Forcing fc{a.forcing, a.snowflag, a.ncell, id.c, o.NR + 1, a.fcol[g], a.ncol};
   const Soil3 s3 = load_soil3(cv);
   HruWork<NN> w;
   StepConst C;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
   if (!FIRST && (a.hstate[g] & HS_STATE) != 2) return;
   CellView cv{a.cell_params, a.ncell, id.c, o.Nnode, o.Nband};
   VegLib vl{a.veglib};
-  Forcing fc{a.forcing, a.snowflag, a.ncell, id.c, o.NR + 1};
+  Forcing fc{a.forcing, a.snowflag, a.ncell, id.c, o.NR + 1, a.fcol[g], a.ncol};
   const Soil3 s3 = load_soil3(cv);
   const int Nn = node_count<NN>(o.Nnode);
   const CtxRef cx = CtxRef::at(a.ctx, ctx_words<NN>(), g);
@@ -409,7 +409,9 @@ struct EArgs {
   const int* npend_cur;   // the number of evaluations pending, written by the round's profile kernel
   int implicit;          // IMPLICIT: the final evaluation is always solved again (its fallback flags depend on the solves before it)
   const double* veglib;  // for the table-derived part of the residual's inputs (surf_cell_fill)
-  const double* forcing; // this step
+  const double* forcing; // this step: [VIC_NFORCE][NF+1][ncol]
+  const int* fcol;        // [nhru] forcing column of each HRU's cell (KArgs)
+  int ncol;
   int month;
 };
 
@@ -474,7 +476,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void v
   }
   {
     const VegLib vl{a.veglib};
-    const Forcing fc{a.forcing, nullptr, a.ncell, c, a.o.NR + 1};
+    const Forcing fc{a.forcing, nullptr, a.ncell, c, a.o.NR + 1, a.fcol[g], a.ncol};
     surf_cell_fill(eb, cv, vl, s3, fc, eb.hidx, veg_idx, a.month);
   }
   const double* __restrict__ rec = a.pout + (size_t)g * pout_hru_stride(a.Nn);

@@ -74,6 +74,13 @@ struct Domain {
   // with a retire mask; until then the kernels get a null table (valid_table) and take no load for it
   DevBuf<int> d_valid;
   bool valid_live = false;
+  // forcing map (vicgpu_set_forcing_map): cell -> forcing column.  Identity after vicgpu_set_domain: ncol == ncell, no buffer,
+  // and the kernels take the HPI_CELL row as the HRUs' column row (forcing_col_row).  With a map: the host copy, its device
+  // copy for the kernels whose lane is a cell, and the derived row cell_col[HPI_CELL] for those whose lane is an HRU
+  int ncol = 0;
+  std::vector<int> cell_col;       // empty: identity
+  DevBuf<int> d_cell_col;          // [ncell]
+  DevBuf<int> d_hru_fcol;          // [nhru]
   // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
   bool fd = false;
   DevBuf<unsigned long long> d_ctx;
@@ -214,14 +221,23 @@ static void free_records(vicgpu_ctx* c) {
   c->rec = Records();
 }
 
-static void free_domain(vicgpu_ctx* c) {
-  free_records(c);
-  c->dom = Domain();
-  c->chunk_steps = 0;              // a forcing chunk belongs to the domain it was pushed for (its rows are ncell wide)
+// A forcing chunk belongs to the domain and the forcing map it was pushed for (its rows are ncol resp. ncell wide): both
+// slots are dropped, their memory stays
+static void drop_forcing(vicgpu_ctx* c) {
+  c->chunk_steps = 0;
   c->dmy.clear();
   c->cur = c->staged = -1;
   c->d_forcing = nullptr; c->d_snowflag = nullptr;
 }
+
+static void free_domain(vicgpu_ctx* c) {
+  free_records(c);
+  c->dom = Domain();
+  drop_forcing(c);
+}
+
+// the HRUs' forcing columns as the kernels take them: the derived row of a map, the HPI_CELL row without one
+static const int* forcing_col_row(const Domain& d) { return d.d_hru_fcol ? d.d_hru_fcol.get() : d.d_hpi.get() + (size_t)HPI_CELL * d.nhru; }
 
 template <int NN>
 static hipError_t launch_hru(const KArgs& ka, hipStream_t st, bool ordinary, bool glacier) {
@@ -319,6 +335,7 @@ static KArgs make_kargs(const vicgpu_ctx* c) {
   ka.hru_err = d.d_hru_err; ka.ctx = d.d_ctx; ka.pin = d.d_pin; ka.ts = d.d_ts; ka.pout = d.d_pout; ka.pslot = d.d_pslot;
   ka.hstate = d.d_hstate; ka.hkey = d.d_hkey; ka.pimp = d.d_pimp; ka.lastexp = d.d_lastexp; ka.jl = d.d_jl;
   ka.valid = valid_table(c);
+  ka.fcol = forcing_col_row(d); ka.ncol = d.ncol;
   return ka;
 }
 static CArgs make_cargs(const vicgpu_ctx* c) {
@@ -347,7 +364,7 @@ static EArgs eval_args(const vicgpu_ctx* c, const FdChunk* ch, const KArgs& ka) 
   ea.pout = d.d_pout; ea.pslot = d.d_pslot; ea.ts = d.d_ts; ea.jl = d.d_jl; ea.hstate = d.d_hstate; ea.hkey = d.d_hkey;
   ea.list_cap = ch->list_cap; ea.pend_cap = ch->pend_cap; ea.profile_next = ch->d_count + CNT_CURSOR;
   ea.pend_prefix = ch->d_count + CNT_PREFIX; ea.npend_cur = ch->d_count + CNT_NPEND; ea.implicit = c->o.IMPLICIT;
-  ea.veglib = c->d_veglib; ea.forcing = ka.forcing; ea.month = ka.dmy.month;
+  ea.veglib = c->d_veglib; ea.forcing = ka.forcing; ea.fcol = ka.fcol; ea.ncol = ka.ncol; ea.month = ka.dmy.month;
   return ea;
 }
 static IArgs implicit_args(const vicgpu_ctx* c, const FdChunk* ch) {
@@ -449,7 +466,8 @@ static hipError_t launch_put_data(const vicgpu_ctx* c, hipStream_t st, int c0, i
   a.rec = s < 0 ? -1 : 0; a.out_step_ratio = c->out_step_ratio;
   a.cell_off = c->dom.d_cell_off; a.cell_list = c->dom.d_cell_list; a.cell_params = c->dom.d_cp; a.veglib = c->d_veglib;
   a.hpi = c->dom.d_hpi; a.hpd = c->dom.d_hpd; a.sd = c->dom.d_sd; a.si = c->dom.d_si; a.flux = c->dom.d_flux;
-  a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->dom.ncell;
+  a.forcing = s < 0 ? nullptr : c->d_forcing + (size_t)s * VIC_NFORCE * (c->o.NR + 1) * c->dom.ncol;
+  a.cell_col = c->dom.d_cell_col; a.ncol = c->dom.ncol;
   a.cell_out = c->dom.d_cell_out; a.out_data = c->dom.d_out_data; a.out_agg = c->dom.d_out_agg; a.pb = c->dom.d_pb;
   a.valid = valid_table(c);
   const unsigned nblk = (unsigned)((ccount + 63) / 64);
@@ -506,7 +524,7 @@ static hipError_t records_emit(vicgpu_ctx* c, int lane, hipStream_t st, int c0, 
 
 static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
   const size_t nsub = c->o.NR + 1;
-  ka.forcing = c->d_forcing + (size_t)s * VIC_NFORCE * nsub * c->dom.ncell;
+  ka.forcing = c->d_forcing + (size_t)s * VIC_NFORCE * nsub * c->dom.ncol;      // values per column, flags per cell
   ka.snowflag = c->d_snowflag + (size_t)s * nsub * c->dom.ncell;
   const int* d = &c->dmy[(size_t)s * VIC_NDMY];
   ka.dmy.month = d[VIC_DMY_MONTH]; ka.dmy.day_in_year = d[VIC_DMY_DAY_IN_YEAR]; ka.dmy.hour = d[VIC_DMY_HOUR];

@@ -60,7 +60,9 @@ struct OArgs {
   const double* sd;
   const int* si;
   const double* flux;
-  const double* forcing;        // this step: [VIC_NFORCE][NF+1][ncell] (unused when rec < 0)
+  const double* forcing;        // this step: [VIC_NFORCE][NF+1][ncol] (unused when rec < 0)
+  const int* cell_col;          // [ncell] forcing column of every cell (vicgpu_set_forcing_map), or null: column = cell
+  int ncol;                     // forcing columns; ncell without a map
   const double* cell_out;       // [CO_NROW][ncell]
   double* out_data;             // [nrow][ncell]
   double* out_agg;              // [nrow][ncell]
@@ -453,7 +455,10 @@ __global__ __launch_bounds__(64) void vic_put_finish(const OArgs a) {
                save_surfstor = PB(PB_SAVE_SURFSTOR), last_storage = PB(PB_WATER_LAST_STORAGE);
   double prec = 0;
   if (a.rec >= 0) {                                                                   // put_data.c:229-256
-#define FV(var) a.forcing[((size_t)(var) * ns + NR) * nc + c]
+    // the forcing echoes are the cell's column's (the lane is a cell: the map itself, no derived row)
+    const size_t ncol = a.ncol;
+    const int col = a.cell_col ? a.cell_col[c] : c;
+#define FV(var) a.forcing[((size_t)(var) * ns + NR) * ncol + col]
     const double vp = FV(VIC_F_VP), vpd = FV(VIC_F_VPD), pr = FV(VIC_F_PRESSURE);
     prec = a.cell_out[(size_t)CO_OUT_PREC * nc + c];
     ROW(AIR_TEMP, 0) = FV(VIC_F_AIR_TEMP); ROW(DENSITY, 0) = FV(VIC_F_DENSITY); ROW(LONGWAVE, 0) = FV(VIC_F_LONGWAVE);

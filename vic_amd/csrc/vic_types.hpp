@@ -157,12 +157,14 @@ struct CellView {
   VIC_DEV double zwt_moist(int l, int i) const { return s(VICGPU_CP_ZWT_MOIST(l, i, Nn, Nb)); }
 };
 
-// forcing of one record for this lane's cell: [VIC_NFORCE][NF+1][ncell]
+// forcing of one record for this lane's cell: the values [VIC_NFORCE][NF+1][ncol] in the cell's forcing column
+// (vicgpu_set_forcing_map; col == c and ncol == ncell without a map), the flags per cell
 struct Forcing {
   const double* __restrict__ f;
   const unsigned char* __restrict__ snowflag;   // [NF+1][ncell]
   int ncell, c, nsub;
-  VIC_DEV double v(int var, int sub) const { return f[((size_t)var * nsub + sub) * ncell + c]; }
+  int col, ncol;
+  VIC_DEV double v(int var, int sub) const { return f[((size_t)var * nsub + sub) * ncol + col]; }
   VIC_DEV int flag(int sub) const { return snowflag[(size_t)sub * ncell + c]; }
 };
 

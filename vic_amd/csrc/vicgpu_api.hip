@@ -138,6 +138,7 @@ static int set_domain_impl(vicgpu_ctx* c, int ncell, int nhru, const double* cel
   free_domain(c);
   c->tune = read_tuning(c->opt.NODE_SOLVER, ncell);
   c->dom.ncell = ncell; c->dom.nhru = nhru;
+  c->dom.ncol = ncell;             // the forcing map of a fresh domain is the identity
   c->dom.fd = !c->o.QUICK_FLUX;
   int r = domain_tables(c, cell_params, hpi, hpd, cell_hru_offset, cell_hru_list);
   if (r == VICGPU_OK && c->dom.fd) r = domain_fd_workspace(c);
@@ -201,9 +202,10 @@ static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, 
   return hipMemcpy2DAsync(dst, width, src, pitch, width, rows, hipMemcpyHostToDevice, c->copy_stream);
 }
 
-// ld: cells per row of the source tables (c->dom.ncell, or the global cell count when a group uploads one shard's columns)
+// ld: columns per row of the source forcing / raw tables (c->dom.ncol, or the global column count when a group uploads one
+// shard's columns); ld_flag: cells per row of the source flags (c->dom.ncell, or the global cell count)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
-                         const int* dmy, double min_wind, int plapse, int ld) {
+                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag) {
   if (!c || nsteps <= 0 || !dmy || (!raw && (!forcing || !snowflag))) return VICGPU_ERR_ARG;
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
@@ -212,8 +214,9 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
     if (m < 1 || m > 12) return VICGPU_ERR_ARG;          // month indexes the veg library tables
   }
   const size_t nsub = c->o.NR + 1;
-  const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell, nf = VIC_NFORCE * sbytes;      // flags (a byte each) and forcing values
-  const size_t nraw = raw ? (size_t)nsteps * VIC_NRAW * c->o.dt * c->dom.ncell : 0;
+  const size_t ncol = c->dom.ncol;                                                            // values per column, flags per cell
+  const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell, nf = (size_t)VIC_NFORCE * nsteps * nsub * ncol;      // flags (a byte each) and forcing values
+  const size_t nraw = raw ? (size_t)nsteps * VIC_NRAW * c->o.dt * ncol : 0;
   const size_t fbytes = sizeof(double) * nf, rbytes = sizeof(double) * nraw;                   // in the staging area
   const int t = (c->cur == 0) ? 1 : 0;
   vicgpu_ctx::ForcingSlot& sl = c->slot[t];
@@ -232,18 +235,23 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
   const size_t need_stage = raw ? (is_pinned(raw) ? 0 : rbytes) : ((is_pinned(forcing) ? 0 : fbytes) + (is_pinned(snowflag) ? 0 : sbytes));
   HIPCHK(c, sl.h_stage.reserve(need_stage));
   if (raw) {
-    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * c->dom.ncell, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * ncol, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
     FArgs a;
     a.nsteps = nsteps; a.ncell = c->dom.ncell; a.dt = c->o.dt; a.snow_step = c->o.snow_step; a.NF = c->o.NF; a.NR = c->o.NR;
     a.temp_th_type = c->o.TEMP_TH_TYPE; a.Nband = c->o.Nband; a.Nnode = c->o.Nnode; a.plapse = plapse;
+    a.ncol = c->dom.ncol; a.cell_col = c->dom.d_cell_col;
     a.min_wind = (double)(float)min_wind;        // options.MIN_WIND_SPEED is a float (vicNl_def.h:713)
     a.raw = sl.d_raw; a.cell_params = c->dom.d_cp; a.forcing = sl.d_f; a.snowflag = sl.d_s;
-    const size_t n = (size_t)nsteps * c->dom.ncell;
-    hipLaunchKernelGGL(vic_derive_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
+    const size_t n = (size_t)nsteps * c->dom.ncell, nc = (size_t)nsteps * ncol;
+    if (!c->dom.d_cell_col) hipLaunchKernelGGL(vic_derive_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
+    else {                                       // the rows once per column, then every cell's flag from its column's rows
+      hipLaunchKernelGGL(vic_derive_forcing_cols, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->copy_stream, a);
+      hipLaunchKernelGGL(vic_derive_forcing_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
+    }
     HIPCHK(c, hipGetLastError());
   } else {
-    HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * c->dom.ncell, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
-    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->dom.ncell, (size_t)nsteps * nsub, ld, is_pinned(forcing) ? 0 : fbytes));
+    HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * ncol, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->dom.ncell, (size_t)nsteps * nsub, ld_flag, is_pinned(forcing) ? 0 : fbytes));
   }
   HIPCHK(c, hipEventRecord(sl.uploaded, c->copy_stream));
   sl.upload_pending = true;
@@ -255,11 +263,11 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
 }
 
 int vicgpu_prefetch_forcing(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const int* dmy) {
-  return c ? prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1, c->dom.ncell) : VICGPU_ERR_ARG;
+  return c ? prefetch_impl(c, nsteps, forcing, snowflag, nullptr, dmy, 0.0, 1, c->dom.ncol, c->dom.ncell) : VICGPU_ERR_ARG;
 }
 int vicgpu_prefetch_forcing_raw(vicgpu_ctx* c, int nsteps, const double* raw, const int* dmy, double min_wind_speed, int plapse) {
   if (!raw) return VICGPU_ERR_ARG;
-  return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->dom.ncell) : VICGPU_ERR_ARG;
+  return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->dom.ncol, c->dom.ncell) : VICGPU_ERR_ARG;
 }
 
 int vicgpu_swap_forcing(vicgpu_ctx* c) {
@@ -288,11 +296,53 @@ int vicgpu_get_forcing(vicgpu_ctx* c, int step, double* forcing, unsigned char* 
   if (!c || !forcing || !snowflag) return VICGPU_ERR_ARG;
   if (c->cur < 0 || step < 0 || step >= c->chunk_steps) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t nflag = (size_t)(c->o.NR + 1) * c->dom.ncell, nforce = VIC_NFORCE * nflag;      // of one step
+  const size_t nflag = (size_t)(c->o.NR + 1) * c->dom.ncell, nforce = (size_t)VIC_NFORCE * (c->o.NR + 1) * c->dom.ncol;      // of one step
   const vicgpu_ctx::ForcingSlot& sl = c->slot[c->cur];      // d_forcing / d_snowflag are views of its buffers
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, sl.d_f.download(c->stream, forcing, step * nforce, nforce));
   HIPCHK(c, sl.d_s.download(c->stream, snowflag, step * nflag, nflag));
+  return VICGPU_OK;
+}
+
+// ---- forcing map: cell -> forcing column (ensembles, a model grid finer than its forcing grid)
+int vicgpu_set_forcing_map(vicgpu_ctx* c, int ncol, const int* cell_col) {
+  if (!c) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  Domain& d = c->dom;
+  if (cell_col) {
+    if (ncol < 1) return VICGPU_ERR_ARG;
+    for (int i = 0; i < d.ncell; i++)
+      if (cell_col[i] < 0 || cell_col[i] >= ncol) return VICGPU_ERR_ARG;      // the map and the chunk in force stay
+  } else if (ncol != 0 && ncol != d.ncell) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the steps queued so far ran on the map as it was
+  HIPCHK(c, hipStreamSynchronize(c->copy_stream)); // and a prefetch in flight fills a slot of the old width
+  DevBuf<int> cols, fcol;          // become the domain's only when complete
+  if (cell_col) {
+    HIPCHK(c, cols.alloc(d.ncell));
+    HIPCHK(c, fcol.alloc(d.nhru));
+    HIPCHK(c, cols.upload(c->stream, cell_col));
+    const int* hpi_cell = d.d_hpi + (size_t)HPI_CELL * d.nhru;
+    const int* cols_arg = cols;
+    int* fcol_arg = fcol;
+    const int nhru = d.nhru;
+    hipLaunchKernelGGL(vic_fill_hru_fcol, dim3((unsigned)((nhru + 255) / 256)), dim3(256), 0, c->stream, hpi_cell, cols_arg, nhru, fcol_arg);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  d.d_cell_col = std::move(cols); d.d_hru_fcol = std::move(fcol);      // identity: both empty, the old ones released
+  if (cell_col) d.cell_col.assign(cell_col, cell_col + d.ncell); else d.cell_col.clear();
+  d.ncol = cell_col ? ncol : d.ncell;
+  drop_forcing(c);                 // a chunk's rows are as wide as the map it was pushed for
+  return VICGPU_OK;
+}
+
+int vicgpu_get_forcing_map(vicgpu_ctx* c, int* ncol, int* cell_col) {
+  if (!c || !ncol) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  *ncol = c->dom.ncol;
+  if (cell_col)
+    for (int i = 0; i < c->dom.ncell; i++) cell_col[i] = c->dom.cell_col.empty() ? i : c->dom.cell_col[i];
   return VICGPU_OK;
 }
 

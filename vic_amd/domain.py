@@ -444,6 +444,68 @@ def drop_hrus(d, drop):
     return keep
 
 
+def tile_members(d, nmember):
+    """The member-major ensemble domain of `d`: (D, cell_col) with D.ncell = nmember * d.ncell, cell m * d.ncell + j a copy of
+    cell j of `d`, and cell_col[m * d.ncell + j] = j the forcing column it reads (Model.set_forcing_map): nmember parameter
+    sets of the same cells over the same meteorology.  The members start as exact copies; perturb D.cell_params and
+    D.hru_dparams per member afterwards.  HRUs are renumbered slot-major as make_domain numbers them (slot = the HRU's rank
+    among its cell's HRUs: hru = slot * D.ncell + cell for a regular domain), the CSR lists are rebuilt."""
+    M, nc, nh = int(nmember), d.ncell, d.nhru
+    assert M >= 1
+    cell = d.hru_iparams[C["HPI_CELL"]].astype(np.int64)
+    # slot of a base HRU: its rank among the HRUs of its cell, by id
+    order = np.lexsort((np.arange(nh), cell))
+    first = np.searchsorted(cell[order], cell[order], side="left")
+    slot = np.empty(nh, dtype=np.int64)
+    slot[order] = np.arange(nh) - first
+    ncell = M * nc
+    # (member, base HRU) -> key slot * ncell + new cell; the new id is the key's rank (the key itself for a regular domain)
+    key = slot[None, :] * ncell + (np.arange(M)[:, None] * nc + cell[None, :])
+    rank = np.empty(M * nh, dtype=np.int64)
+    rank[np.argsort(key.reshape(-1), kind="stable")] = np.arange(M * nh)
+    newid = rank.reshape(M, nh)
+    D = Domain()
+    D.opt, D.veglib = d.opt, d.veglib
+    D.ncell, D.nhru = ncell, M * nh
+    D.global_cell0, D.ncell_global = 0, ncell
+    if hasattr(d, "nslot"):
+        D.nslot = d.nslot
+    D.cell_params = np.ascontiguousarray(np.tile(d.cell_params, (1, M)))
+    D.init_moist = np.ascontiguousarray(np.tile(d.init_moist, (1, M)))
+    D.elevation = np.tile(d.elevation, M)
+    D.cell_offset_T = np.tile(d.cell_offset_T, M)
+    D.rng_seed = d.rng_seed
+    hpi = np.zeros((C["HPI_NROW"], D.nhru), dtype=np.int32)
+    hpd = np.zeros((C["HPD_NROW"], D.nhru))
+    for m in range(M):
+        hpi[:, newid[m]] = d.hru_iparams
+        hpi[C["HPI_CELL"], newid[m]] = m * nc + cell
+        hpd[:, newid[m]] = d.hru_dparams
+    D.hru_iparams = np.ascontiguousarray(hpi)
+    D.hru_dparams = np.ascontiguousarray(hpd)
+    per_cell = np.diff(d.cell_hru_offset)
+    D.cell_hru_offset = np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.tile(per_cell, M))]).astype(np.int32))
+    D.cell_hru_list = np.ascontiguousarray(np.concatenate([newid[m][d.cell_hru_list] for m in range(M)]).astype(np.int32))
+    return D, np.ascontiguousarray(np.tile(np.arange(nc, dtype=np.int32), M))
+
+
+def make_snowflag(d, forcing, cell_col=None):
+    """The per-cell snowflag uint8[nsteps][NF+1][ncell] of a derived forcing table (initialize_atmos.c:1275-1303): cell c from its
+    own parameters and the air temperature and precipitation of its column cell_col[c] (None: its own column)."""
+    opt = d.opt
+    NF, NR, Nn, Nb = opt.NF, opt.NR, opt.Nnode, opt.Nband
+    col = np.arange(d.ncell) if cell_col is None else np.asarray(cell_col)
+    min_tf = np.stack([d.cell_params[abi.cp_band(C["CPB_TFACTOR"], b, Nn, Nb)] for b in range(Nb)]).min(axis=0)
+    max_snow, min_rain = d.cell_params[C["CP_MAX_SNOW_TEMP"]], d.cell_params[C["CP_MIN_RAIN_TEMP"]]
+    thr = max_snow + min_rain / 2 if opt.TEMP_TH_TYPE == C["VIC_TEMP_TH_KIENZLE"] else max_snow
+    T, prec = forcing[:, C["VIC_F_AIR_TEMP"], :NF][..., col], forcing[:, C["VIC_F_PREC"], :NF][..., col]
+    sflag = np.zeros((forcing.shape[0], NR + 1, d.ncell), dtype=np.uint8)
+    sflag[:, :NF] = ((T + min_tf) < thr) & (prec > 0)
+    if NR > 0:
+        sflag[:, NR] = sflag[:, :NF].max(axis=1)
+    return np.ascontiguousarray(sflag)
+
+
 def svp(T):
     """svp.c:7-24 (Pa)."""
     T = np.asarray(T, dtype=float)
