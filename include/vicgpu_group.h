@@ -89,7 +89,10 @@ int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);
 /* the record entries of vicgpu_out.h: out [nrecords][nrow][ncell] and cell_err [nrecords][ncell] are the caller's global
- * tables in pinned memory, every shard delivers its own columns by pitched copies; wait(k) waits for every shard */
+ * tables in pinned memory, every shard delivers its own columns by pitched copies; wait(k) waits for every shard.
+ * The cell groups of vicgpu_records_set_groups have no group form: a group of cells that spans shards would need a summation
+ * order across devices, which is a decision of its own.  vicgpu_group_run_records returns VICGPU_ERR_STATE when a shard's
+ * context (vicgpu_group_shard_ctx) has groups set. */
 int vicgpu_group_records_config(vicgpu_group *g, int nvar, const int *var_ids, int depth);
 int vicgpu_group_records_nrow(vicgpu_group *g);
 int vicgpu_group_run_records(vicgpu_group *g, int step0, int nrecords, float *out, int *cell_err);

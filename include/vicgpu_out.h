@@ -162,6 +162,36 @@ int vicgpu_run_records(vicgpu_ctx *ctx, int step0, int nrecords,
                        int *cell_err);                 /* [nrecords][ncell] from vicgpu_host_alloc, or NULL */
 int vicgpu_records_wait(vicgpu_ctx *ctx, int k);       /* record k of the last vicgpu_run_records has landed; k = -1: all */
 
+/* Records reduced over cell groups on the device: a sparse, weighted map from cell columns to output columns (basin sums of
+ * an ensemble's members; a full lat/lon grid with a fill value where no cell is modelled).
+ *
+ * The groups are part of the records configuration: set after vicgpu_records_config, dropped by whatever drops or replaces it
+ * (another vicgpu_records_config, nvar = 0, vicgpu_put_data_config, vicgpu_set_domain); ngroup = 0 with NULL pointers removes
+ * them.  A cell may be in several groups or in none and may repeat within a group; member order is the caller's and decides
+ * the summation order.  With groups set vicgpu_run_records delivers out as [nrecords][nrow][ngroup]; cell_err stays
+ * [nrecords][ncell]; state, fluxes, aggregates (zero after the call), balance, accumulators, vicgpu_last_kernel_ms and
+ * vicgpu_get_outputs are what they are without groups.  A retired cell contributes what its record holds (zeros after
+ * retirement).  The call waits for records still on their way.
+ *
+ * What a grouped record holds.  v[r][c] is the float the ungrouped record holds for row r and cell c.  Group g has the members
+ * i = 0 .. n-1 in list order with the terms t_i = w_i * (double)v[r][cell_i], each rounded once (never contracted).  n == 0:
+ * the value is `fill`.  Otherwise lane l of 64 forms p_l: its first term t_l is assigned (not added to zero), then t_{l+64},
+ * t_{l+128}, ... are added in that order; a lane without a member holds +0.0.  Then for s = 32, 16, 8, 4, 2, 1:
+ * p_l = p_l + p_{l+s} for l < s.  The value is (float)p_0.  A single-member group of weight 1 reproduces the cell's float
+ * (-0.0 becomes +0.0).  The result depends on nothing else: not on depth, on the cell chunks or on the kernel chosen.
+ *
+ * VICGPU_ERR_STATE: no records configuration (all three entries).  VICGPU_ERR_ARG: a null handle or result pointer,
+ * ngroup < 0, group_off[0] != 0 or decreasing offsets, a cell outside [0, ncell), a weight that is not finite.
+ * VICGPU_ERR_HIP: an allocation was refused.  A failing call leaves the groups in force as they were and nothing behind.
+ * A context with groups set cannot deliver records as a shard of a device group (vicgpu_group.h). */
+int vicgpu_records_set_groups(vicgpu_ctx *ctx, int ngroup,
+                              const int *group_off,       /* [ngroup+1], group_off[0] = 0, non-decreasing; nnz = group_off[ngroup] */
+                              const int *group_cell,      /* [nnz], each in [0, ncell) */
+                              const double *group_weight, /* [nnz], finite; NULL = all 1.0 */
+                              float fill);                /* value of a group without members */
+int vicgpu_records_get_groups(vicgpu_ctx *ctx, int *ngroup, int *nnz);  /* 0, 0 when none is set */
+int vicgpu_records_ncol(vicgpu_ctx *ctx);  /* columns of a record: ngroup when groups are set, else ncell; < 0 = error code */
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,9 @@ def load_library():
         "vicgpu_records_nrow": (ctypes.c_int, [vp]),
         "vicgpu_run_records": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), _ip]),
         "vicgpu_records_wait": (ctypes.c_int, [vp, ctypes.c_int]),
+        "vicgpu_records_set_groups": (ctypes.c_int, [vp, ctypes.c_int, _ip, _ip, _dp, ctypes.c_float]),
+        "vicgpu_records_get_groups": (ctypes.c_int, [vp, _ip, _ip]),
+        "vicgpu_records_ncol": (ctypes.c_int, [vp]),
         # include/vicgpu_group.h
         "vicgpu_group_partition": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, _ip]),
         "vicgpu_group_create": (ctypes.c_int, [ctypes.POINTER(abi.Options), ctypes.c_int, _ip, ctypes.POINTER(vp)]),
@@ -161,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_put_data_config", "vicgpu_put_data_init", "vicgpu_get_outputs", "vicgpu_get_output_data", "vicgpu_get_balance",
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
     "vicgpu_records_config", "vicgpu_records_nrow", "vicgpu_run_records", "vicgpu_records_wait",
+    "vicgpu_records_set_groups", "vicgpu_records_get_groups", "vicgpu_records_ncol",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
     "vicgpu_set_forcing_map", "vicgpu_get_forcing_map",
@@ -176,16 +180,17 @@ def _i(a):
 
 
 class Records:
-    """The records of one Model.run_records call: `.out` float32 [nrecords][nrow][ncell] and `.errors` int32 [nrecords][ncell]
+    """The records of one Model.run_records call: `.out` float32 [nrecords][nrow][ncol] (ncol = Model.records_ncol(): the
+    cells, or the cell groups of Model.records_set_groups) and `.errors` int32 [nrecords][ncell]
     (None unless asked for) over pinned memory that the copies land in while later records are still being computed.
     Record k may be read after `wait(k)`, everything after `wait()`.  The memory lives as long as this object."""
 
-    def __init__(self, model, nrecords, nrow, errors):
+    def __init__(self, model, nrecords, nrow, errors, ncol=None):
         self._model = model          # keeps the library and the context alive while copies may be in flight
         self._lib = model.lib
         self._ptrs = []
         self.nrecords = nrecords
-        self.out = self._pinned((nrecords, nrow, model.dom.ncell), np.float32)
+        self.out = self._pinned((nrecords, nrow, model.dom.ncell if ncol is None else ncol), np.float32)
         self.errors = self._pinned((nrecords, model.dom.ncell), np.int32) if errors else None
 
     def _pinned(self, shape, dtype):
@@ -454,10 +459,35 @@ class Model:
         + get_cell_errors give record by record, delivered while the following records run.  Returns a Records."""
         nrow = self.lib.vicgpu_records_nrow(self.h)
         self._chk(min(nrow, 0))
-        rec = Records(self, int(nrecords), nrow, errors)
+        rec = Records(self, int(nrecords), nrow, errors, self.records_ncol())
         self._chk(self.lib.vicgpu_run_records(self.h, int(step0), int(nrecords), rec.out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                               _i(rec.errors) if errors else None))
         return rec
+
+    def records_set_groups(self, offsets, cells, weights=None, fill=0.0):
+        """vicgpu_records_set_groups: the records of run_records become [nrow][ngroup], group g the weighted sum (in the
+        order include/vicgpu_out.h states) of the cells cells[offsets[g]:offsets[g + 1]]; weights None: all 1.0; `fill`: the
+        value of a group without members.  offsets None (or empty): the groups are removed."""
+        if offsets is None or len(offsets) == 0:
+            self._chk(self.lib.vicgpu_records_set_groups(self.h, 0, None, None, None, float(fill)))
+            return
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        cell = np.ascontiguousarray(cells, dtype=np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        assert off.ndim == 1 and cell.shape == (int(off[-1]),) and (w is None or w.shape == cell.shape), (off.shape, cell.shape)
+        self._chk(self.lib.vicgpu_records_set_groups(self.h, len(off) - 1, _i(off), _i(cell), None if w is None else _d(w), float(fill)))
+
+    def records_get_groups(self):
+        """(ngroup, nnz) of the groups in force; (0, 0) when none is set."""
+        ng, nnz = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.vicgpu_records_get_groups(self.h, ctypes.byref(ng), ctypes.byref(nnz)))
+        return ng.value, nnz.value
+
+    def records_ncol(self):
+        """Columns of a record: the groups when groups are set, else the cells."""
+        n = self.lib.vicgpu_records_ncol(self.h)
+        self._chk(min(n, 0))
+        return n
 
     def get_balance(self):
         pb = np.zeros((C["PB_NROW"], self.dom.ncell))
@@ -565,6 +595,16 @@ class Group(Model):
         b = np.zeros(len(self.devices) + 1, dtype=np.int32)
         self._chk(self.lib.vicgpu_group_shard_bounds(self.h, _i(b)))
         return b
+
+    # ---- cell groups of the records have no device-group form (include/vicgpu_group.h)
+    def records_set_groups(self, offsets, cells, weights=None, fill=0.0):
+        raise VicGpuError("records_set_groups has no device-group form: a cell group that spans shards has no summation order")
+
+    def records_get_groups(self):
+        return 0, 0
+
+    def records_ncol(self):
+        return self.dom.ncell
 
     def shard_ctx(self, k):
         """Shard k's vicgpu_ctx handle, for the per-context entries (stream, tuning, debug)."""

@@ -478,6 +478,9 @@ int vicgpu_group_records_nrow(vicgpu_group* g) {
 int vicgpu_group_run_records(vicgpu_group* g, int step0, int nrecords, float* out, int* cell_err) {
   if (!g || !out) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
+  // cell groups (vicgpu_records_set_groups on a shard's context) have no group form: a shard's records are its columns
+  for (vicgpu_ctx* c : g->ctx)
+    if (c->rec.ngroup > 0) return group_fail(g, VICGPU_ERR_STATE, "a shard's records are reduced over cell groups: not supported in a device group");
   // the shards make the same checks on the same arguments before they queue anything, so either all of them run or none
   const int r = group_each(g, [&](int k) {
     return run_records_impl(g->ctx[k], step0, nrecords, out + g->c0(k), cell_err ? cell_err + g->c0(k) : nullptr, g->ncell);

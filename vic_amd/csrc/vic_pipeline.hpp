@@ -10,6 +10,9 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "vicgpu.h"
@@ -107,7 +110,7 @@ struct Tuning {
   bool xcd_map = true;             // VICGPU_NO_XCD_MAP (set): plain instead of XCD-aware launch order
   bool trace_rounds = false;       // VICGPU_TRACE_ROUNDS (set): what every round leaves pending (a host round trip per round)
   bool trace = false;              // VICGPU_TRACE (set): per-step wall time and Brent rounds (a wait per step)
-  bool stats = false;              // VICGPU_STATS (set): Brent rounds per step of every chunk, printed by vicgpu_destroy
+  bool stats = false;              // VICGPU_STATS (set): Brent rounds per step of every chunk, printed by vicgpu_destroy; the record groups' reduce time
 };
 static Tuning read_tuning(int node_solver, int ncell) {
   Tuning t;
@@ -149,13 +152,60 @@ static Tuning read_tuning(int node_solver, int ncell) {
 // delay a record).  In the finite-difference pipeline the context's stream, which is idle while the chunks' streams run the
 // steps: a fifth stream made two of them share one of the process's four hardware queues, and the two chunks of a 100k-cell
 // domain then ran one after the other (28.9 instead of 22.1 ms per step).
+//
+// Cell groups (vicgpu_records_set_groups): the record that travels is [nrow][ngroup], reduced from the slot's packed
+// [nrow][ncell] by one kernel on the download stream.  A group may span lanes, so record k's reduction is a join: it is
+// queued once, behind every lane's `packed` event of record k, by the lane that arrives last (RecordsJoin), followed by one
+// contiguous copy and `reduced[k]`.  It reads every lane's columns of the slot, so no lane may pack record k + depth before
+// it: a lane that runs ahead waits on the host until the join of record k has been queued, then queues its wait for
+// reduced[k].  Each lane still copies its own cell_err columns.
+
+// Host-side order of the lanes around the joins of one vicgpu_run_records call.  hipStreamWaitEvent on an event that has not
+// been recorded yet is a no-op, so who queues a join must know that every lane has recorded its `packed` event: the last of
+// the nlane arrivals at record k does.  The joins are queued in record order (a lane arrives at k + 1 only after it has left
+// k).  A lane that fails releases the others, which return its status.
+struct RecordsJoin {
+  std::mutex m;
+  std::condition_variable cv;
+  std::vector<int> arrived;        // [records of the call]: lanes that have queued their part of record k
+  int queued = 0;                  // the joins of the records [0, queued) are on the download stream
+  int status = 0;                  // != 0: a lane has failed
+  std::string err;
+  void start(int nrecords) { arrived.assign(nrecords, 0); queued = 0; status = 0; err.clear(); }
+  // true for the last of nlane arrivals at record k
+  bool arrive(int k, int nlane) { std::lock_guard<std::mutex> lk(m); return ++arrived[k] == nlane; }
+  void join_queued(int k) { { std::lock_guard<std::mutex> lk(m); queued = k + 1; } cv.notify_all(); }
+  // blocks until the join of record k is queued; the failing lane's status when one has failed
+  int wait_queued(int k, std::string* why) {
+    std::unique_lock<std::mutex> lk(m);
+    cv.wait(lk, [&]() { return queued > k || status != 0; });
+    if (status != 0) *why = err;
+    return status;
+  }
+  void fail(int st, const std::string& why) {
+    { std::lock_guard<std::mutex> lk(m); if (status == 0) { status = st; err = why; } }
+    cv.notify_all();
+  }
+};
+
 struct Records {
   int nrow = 0, depth = 0;         // rows of a record; depth == 0: not configured
   DevBuf<int> d_sel_pos;           // [out_nrow]: the record row of an aggregate row, or -1
   struct Slot {
     DevBuf<float> d_out;           // [nrow][ncell]
     DevBuf<int> d_err;             // [ncell]
+    DevBuf<float> d_group;         // [nrow][ngroup], with groups
   };
+  // cell groups: ngroup == 0: none.  CSR over the cells, the weights as given (1.0 where the caller passed none)
+  int ngroup = 0, nnz = 0;
+  float fill = 0.0f;
+  bool lane_per_group = false;     // no group has more than one member: vic_out_group_reduce_lane
+  DevBuf<int> d_group_off, d_group_cell;
+  DevBuf<double> d_group_weight;
+  std::vector<Event> reduced;      // [records of the largest call]: record k's [nrow][ngroup] is in the caller's table
+  std::unique_ptr<RecordsJoin> join;
+  Event reduce_t0, reduce_t1;      // VICGPU_STATS: around the reduction of a call's last record
+  bool reduce_timed = false;       // ... both have been recorded
   std::vector<Slot> slot;
   int nlane = 0;
   std::vector<Event> packed;       // [nlane][depth]: the slot holds the lane's columns of its record
@@ -215,9 +265,21 @@ static int* valid_table(const vicgpu_ctx* c) { return c->dom.valid_live ? c->dom
 // the stream that carries the output records to the host (see Records)
 static hipStream_t records_stream(const vicgpu_ctx* c) { return c->rec.dl ? (hipStream_t)c->rec.dl : (hipStream_t)c->stream; }
 
+// tuning (VICGPU_STATS): what the reduction over the groups in force took for the last record of the last call; the download
+// stream has been waited for
+static void records_report_reduce(vicgpu_ctx* c) {
+  Records& R = c->rec;
+  float ms = 0;
+  if (R.reduce_timed && hipEventElapsedTime(&ms, R.reduce_t0, R.reduce_t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] records reduce: %d groups, %d members, a %s per group, %d rows: %.4f ms\n", R.ngroup, R.nnz,
+            R.lane_per_group ? "lane" : "wave", R.nrow, ms);
+  R.reduce_timed = false;
+}
+
 // Drops the records configuration; nothing may be left on the download stream
 static void free_records(vicgpu_ctx* c) {
   if (c->rec.depth > 0) HIPIGN(hipStreamSynchronize(records_stream(c)));
+  records_report_reduce(c);
   c->rec = Records();
 }
 
@@ -491,35 +553,75 @@ struct StepPlan {
   int ratio = 0;
 };
 
+// The join of record k with cell groups, queued on the download stream by the last lane to arrive (RecordsJoin): behind every
+// lane's packed event, reduce the slot over the groups, copy the [nrow][ngroup] table to the caller's and record reduced[k]
+static hipError_t records_join(vicgpu_ctx* c, int k) {
+  Records& R = c->rec;
+  const hipStream_t dl = records_stream(c);
+  const int s = k % R.depth;
+  hipError_t e = hipSuccess;
+  for (int lane = 0; lane < R.nlane; lane++)
+    if ((e = hipStreamWaitEvent(dl, R.packed[(size_t)lane * R.depth + s], 0)) != hipSuccess) return e;
+  RGArgs a;
+  a.ncell = c->dom.ncell; a.nrow = R.nrow; a.ngroup = R.ngroup;
+  a.off = R.d_group_off; a.cell = R.d_group_cell; a.weight = R.d_group_weight;
+  a.slot_out = R.slot[s].d_out; a.group_out = R.slot[s].d_group; a.fill = R.fill;
+  const bool timed = c->tune.stats && k == R.last_nrecords - 1;      // tuning: the reduction's own time (records_report_reduce)
+  if (timed && (e = hipEventRecord(R.reduce_t0, dl)) != hipSuccess) return e;
+  const unsigned ntile = (unsigned)((R.nrow + RG_ROWS - 1) / RG_ROWS);
+  if (R.lane_per_group) hipLaunchKernelGGL(vic_out_group_reduce_lane, dim3((unsigned)((R.ngroup + 63) / 64), ntile), dim3(64), 0, dl, a);
+  else hipLaunchKernelGGL(vic_out_group_reduce, dim3((unsigned)R.ngroup, ntile), dim3(64), 0, dl, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (timed && (e = hipEventRecord(R.reduce_t1, dl)) != hipSuccess) return e;
+  R.reduce_timed = R.reduce_timed || timed;
+  const size_t n = (size_t)R.nrow * R.ngroup;
+  if ((e = hipMemcpyAsync(R.out + (size_t)k * n, R.slot[s].d_group, sizeof(float) * n, hipMemcpyDeviceToHost, dl)) != hipSuccess) return e;
+  return hipEventRecord(R.reduced[k], dl);
+}
+
 // The end of record k for the cells [c0, c0 + ccount) of one lane, whose steps ran on `st`: once the slot's previous record
-// has been downloaded, pack the aggregates into slot k % depth and zero them; the download stream copies the lane's
-// columns into the caller's tables behind that.
-static hipError_t records_emit(vicgpu_ctx* c, int lane, hipStream_t st, int c0, int ccount, int k) {
+// has been downloaded (with groups: reduced), pack the aggregates into slot k % depth and zero them; the download stream
+// copies the lane's columns into the caller's tables behind that (with groups: its cell_err columns, and the lane that
+// arrives last queues the join).  A status, with the text in *err.
+static int records_emit(vicgpu_ctx* c, std::string* err, int lane, hipStream_t st, int c0, int ccount, int k) {
   Records& R = c->rec;
   const hipStream_t dl = records_stream(c);
   const int s = k % R.depth;
   const size_t nc = c->dom.ncell, ld = R.ld;
+  const bool groups = R.ngroup > 0;
+  const auto failed = [&](hipError_t e) { *err = std::string("output record: ") + hipGetErrorString(e); return VICGPU_ERR_HIP; };
   hipError_t e = hipSuccess;
-  if (k >= R.depth) e = hipStreamWaitEvent(st, R.landed[(size_t)lane * R.last_nrecords + (k - R.depth)], 0);
+  if (k >= R.depth && groups) {
+    // the reduction of the slot's last record reads every lane's columns: this lane can only wait for it once it is queued
+    const int r = R.join->wait_queued(k - R.depth, err);
+    if (r != VICGPU_OK) return r;
+    e = hipStreamWaitEvent(st, R.reduced[k - R.depth], 0);
+  } else if (k >= R.depth) e = hipStreamWaitEvent(st, R.landed[(size_t)lane * R.last_nrecords + (k - R.depth)], 0);
   else if (R.follows) e = hipStreamWaitEvent(st, R.drained, 0);      // the slot's last user is a copy of the call before
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess) return failed(e);
   RPArgs a;
   a.ncell = c->dom.ncell; a.nrow = c->dom.out_nrow; a.c0 = c0; a.ccount = ccount;
   a.out_agg = c->dom.d_out_agg; a.sel_pos = R.d_sel_pos; a.cell_err = c->dom.d_cell_err;
   a.slot_out = R.slot[s].d_out; a.slot_err = R.slot[s].d_err;
   hipLaunchKernelGGL(vic_out_pack_reset, dim3((unsigned)((ccount + 63) / 64), (c->dom.out_nrow + PUT_AGG_ROWS - 1) / PUT_AGG_ROWS), dim3(64), 0, st, a);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess) return failed(e);
   const hipEvent_t packed = R.packed[(size_t)lane * R.depth + s];
-  if ((e = hipEventRecord(packed, st)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(dl, packed, 0)) != hipSuccess) return e;
-  float* dst = R.out + (size_t)k * R.nrow * ld + c0;
-  const float* src = R.slot[s].d_out + c0;
-  if ((size_t)ccount == nc && ld == nc) e = hipMemcpyAsync(dst, src, sizeof(float) * nc * R.nrow, hipMemcpyDeviceToHost, dl);
-  else e = hipMemcpy2DAsync(dst, sizeof(float) * ld, src, sizeof(float) * nc, sizeof(float) * ccount, R.nrow, hipMemcpyDeviceToHost, dl);
-  if (e != hipSuccess) return e;
+  if ((e = hipEventRecord(packed, st)) != hipSuccess) return failed(e);
+  if ((e = hipStreamWaitEvent(dl, packed, 0)) != hipSuccess) return failed(e);
+  if (!groups) {
+    float* dst = R.out + (size_t)k * R.nrow * ld + c0;
+    const float* src = R.slot[s].d_out + c0;
+    if ((size_t)ccount == nc && ld == nc) e = hipMemcpyAsync(dst, src, sizeof(float) * nc * R.nrow, hipMemcpyDeviceToHost, dl);
+    else e = hipMemcpy2DAsync(dst, sizeof(float) * ld, src, sizeof(float) * nc, sizeof(float) * ccount, R.nrow, hipMemcpyDeviceToHost, dl);
+    if (e != hipSuccess) return failed(e);
+  }
   if (R.err) e = hipMemcpyAsync(R.err + (size_t)k * ld + c0, R.slot[s].d_err + c0, sizeof(int) * ccount, hipMemcpyDeviceToHost, dl);
-  if (e != hipSuccess) return e;
-  return hipEventRecord(R.landed[(size_t)lane * R.last_nrecords + k], dl);
+  if (e != hipSuccess) return failed(e);
+  if (!groups) e = hipEventRecord(R.landed[(size_t)lane * R.last_nrecords + k], dl);
+  else if (R.join->arrive(k, R.nlane)) {        // every lane has recorded its packed event of record k
+    if ((e = records_join(c, k)) == hipSuccess) R.join->join_queued(k);
+  }
+  return e == hipSuccess ? VICGPU_OK : failed(e);
 }
 
 static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
@@ -532,7 +634,7 @@ static void set_step_inputs(const vicgpu_ctx* c, KArgs& ka, int s) {
 }
 
 // all steps of one vicgpu_step or vicgpu_run_records call for one chunk
-static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
+static int fd_chunk_steps(const StepPlan& plan, FdChunk* ch) {
   vicgpu_ctx* c = plan.c;
   HIPCHK(ch, hipSetDevice(c->device));
   KArgs ka = plan.ka;
@@ -557,11 +659,21 @@ static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
     hipLaunchKernelGGL(vic_cell_reduce, dim3((ch->ccount + 255) / 256), dim3(256), 0, ch->stream, ca);
     HIPCHK(ch, hipGetLastError());
     if (c->dom.put_on) HIPCHK(ch, launch_put_data(c, ch->stream, ch->c0, ch->ccount, s));
-    if (plan.records && (s - plan.step0 + 1) % plan.ratio == 0)
-      HIPCHK(ch, records_emit(c, lane, ch->stream, ch->c0, ch->ccount, (s - plan.step0) / plan.ratio));
+    if (plan.records && (s - plan.step0 + 1) % plan.ratio == 0) {
+      const int re = records_emit(c, &ch->err, lane, ch->stream, ch->c0, ch->ccount, (s - plan.step0) / plan.ratio);
+      if (re != VICGPU_OK) return re;
+    }
   }
   HIPCHK(ch, hipEventRecord(ch->done, ch->stream));
   return VICGPU_OK;
+}
+
+// ... and, with grouped records, a chunk that fails releases the chunks that wait for its part of a record (RecordsJoin)
+static int fd_chunk_run(const StepPlan& plan, FdChunk* ch) {
+  const int r = fd_chunk_steps(plan, ch);
+  Records& R = plan.c->rec;
+  if (r != VICGPU_OK && plan.records && R.ngroup > 0) R.join->fail(r, ch->err);
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------------ vicgpu_set_domain, step by step

@@ -7,7 +7,8 @@
 //   vic_hru_io.hpp       KArgs, LaunchMap and the HRU table I/O
 //   vic_kernels.hpp      vic_hru_step, vic_fd_stage, vic_surf_eval
 //   vic_aux_kernels.hpp  glacier fit, derived cell rows, test hooks, vic_cell_reduce, state records, forcing derivation
-//   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records)
+//   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records); vic_out_group_reduce: its
+//                        reduction over cell groups (vicgpu_records_set_groups)
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -21,6 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <thread>
@@ -112,6 +114,7 @@ void vicgpu_destroy(vicgpu_ctx* c) {
   if (c->stream) HIPIGN(hipStreamSynchronize(c->stream));
   if (c->copy_stream) HIPIGN(hipStreamSynchronize(c->copy_stream));
   if (c->rec.dl) HIPIGN(hipStreamSynchronize(c->rec.dl));
+  records_report_reduce(c);
   if (c->tune.stats)
     for (size_t k = 0; k < c->dom.chunks.size(); k++)
       if (c->dom.chunks[k].steps)
@@ -382,7 +385,10 @@ static int step_impl(vicgpu_ctx* c, int step0, int nsteps, int ratio) {
       HIPCHK(c, hipGetLastError());
       if (c->dom.put_on) HIPCHK(c, launch_put_data(c, c->stream, 0, c->dom.ncell, s));
       c->steps_done++;
-      if (records && i == per - 1) HIPCHK(c, records_emit(c, 0, c->stream, 0, c->dom.ncell, (s - step0) / per));
+      if (records && i == per - 1) {
+        const int re = records_emit(c, &c->err, 0, c->stream, 0, c->dom.ncell, (s - step0) / per);
+        if (re != VICGPU_OK) return re;
+      }
     }
     c->ev_used = per;
     c->ev_steps = per;
@@ -831,6 +837,67 @@ int vicgpu_records_nrow(vicgpu_ctx* c) {
   return c->rec.depth > 0 ? c->rec.nrow : VICGPU_ERR_STATE;
 }
 
+// Cell groups of the records (vicgpu_out.h).  Checks first; then what the groups need is allocated aside, filled once the records
+// still on their way have landed, and handed to the configuration only when complete: a refused call leaves the groups in force.
+int vicgpu_records_set_groups(vicgpu_ctx* c, int ngroup, const int* group_off, const int* group_cell, const double* group_weight, float fill) {
+  if (!c) return VICGPU_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->rec.depth < 1) return VICGPU_ERR_STATE;
+  if (ngroup < 0 || (ngroup > 0 && (!group_off || !group_cell))) return VICGPU_ERR_ARG;
+  int nnz = 0, most = 0;
+  if (ngroup > 0) {
+    if (group_off[0] != 0) return VICGPU_ERR_ARG;
+    for (int g = 0; g < ngroup; g++) {
+      if (group_off[g + 1] < group_off[g]) return VICGPU_ERR_ARG;
+      most = std::max(most, group_off[g + 1] - group_off[g]);
+    }
+    nnz = group_off[ngroup];
+    for (int i = 0; i < nnz; i++)
+      if (group_cell[i] < 0 || group_cell[i] >= c->dom.ncell || (group_weight && !std::isfinite(group_weight[i]))) return VICGPU_ERR_ARG;
+  }
+  Records& R = c->rec;
+  DevBuf<int> d_off, d_cell;
+  DevBuf<double> d_weight;
+  std::vector<DevBuf<float>> d_group(ngroup > 0 ? R.depth : 0);
+  if (ngroup > 0) {
+    const std::vector<double> ones(group_weight ? 0 : nnz, 1.0);
+    HIPCHK(c, d_off.alloc((size_t)ngroup + 1));
+    HIPCHK(c, d_cell.alloc(std::max(nnz, 1)));
+    HIPCHK(c, d_weight.alloc(std::max(nnz, 1)));
+    for (DevBuf<float>& b : d_group) HIPCHK(c, b.alloc((size_t)R.nrow * ngroup));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // a record of the last call may still be on its way
+    HIPCHK(c, hipStreamSynchronize(records_stream(c)));
+    HIPCHK(c, d_off.upload(c->stream, group_off));
+    if (nnz > 0) {
+      HIPCHK(c, d_cell.upload(c->stream, group_cell, 0, nnz));
+      HIPCHK(c, d_weight.upload(c->stream, group_weight ? group_weight : ones.data(), 0, nnz));
+    }
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(records_stream(c)));
+  }
+  records_report_reduce(c);
+  R.d_group_off = std::move(d_off); R.d_group_cell = std::move(d_cell); R.d_group_weight = std::move(d_weight);
+  for (int s = 0; s < R.depth; s++) R.slot[s].d_group = ngroup > 0 ? std::move(d_group[s]) : DevBuf<float>();
+  R.ngroup = ngroup; R.nnz = nnz; R.fill = fill; R.lane_per_group = most <= 1;
+  if (ngroup > 0 && !R.join) R.join.reset(new RecordsJoin);
+  R.last_nrecords = 0;             // nothing of an earlier call is in flight, and its events describe records of another shape
+  return VICGPU_OK;
+}
+
+int vicgpu_records_get_groups(vicgpu_ctx* c, int* ngroup, int* nnz) {
+  if (!c || !ngroup || !nnz) return VICGPU_ERR_ARG;
+  if (c->rec.depth < 1) return VICGPU_ERR_STATE;
+  *ngroup = c->rec.ngroup; *nnz = c->rec.nnz;
+  return VICGPU_OK;
+}
+
+int vicgpu_records_ncol(vicgpu_ctx* c) {
+  if (!c) return VICGPU_ERR_ARG;
+  if (c->rec.depth < 1) return VICGPU_ERR_STATE;
+  return c->rec.ngroup > 0 ? c->rec.ngroup : c->dom.ncell;
+}
+
 // ld: cells per row of `out` and `cell_err` (c->dom.ncell, or the global cell count when a group delivers one shard's columns)
 static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld) {
   if (!c) return VICGPU_ERR_ARG;
@@ -840,12 +907,25 @@ static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, 
   HIPCHK(c, hipSetDevice(c->device));
   if (!out || !is_pinned(out) || (cell_err && !is_pinned(cell_err))) return VICGPU_ERR_ARG;
   Records& R = c->rec;
+  if (R.ngroup > 0 && ld != c->dom.ncell) return VICGPU_ERR_STATE;      // grouped records have no pitched form (vicgpu_group.h)
   // record k's landed event of every lane
   const size_t nev = (size_t)R.nlane * nrecords;
   if (R.landed.size() < nev) {
     const size_t had = R.landed.size();
     R.landed.resize(nev);
     for (size_t i = had; i < nev; i++) HIPCHK(c, R.landed[i].create(hipEventDisableTiming));
+  }
+  if (R.ngroup > 0) {              // record k's reduction over the groups, joined from the lanes (Records)
+    if (R.reduced.size() < (size_t)nrecords) {
+      const size_t had = R.reduced.size();
+      R.reduced.resize(nrecords);
+      for (size_t i = had; i < (size_t)nrecords; i++) HIPCHK(c, R.reduced[i].create(hipEventDisableTiming));
+    }
+    if (c->tune.stats && !R.reduce_t0) {
+      HIPCHK(c, R.reduce_t0.create());
+      HIPCHK(c, R.reduce_t1.create());
+    }
+    R.join->start(nrecords);
   }
   // the first packing kernels of this call reuse slots the last call's copies may still read: they wait for `drained`, which
   // is recorded anew only after them (the steps themselves wait for nothing)
@@ -876,6 +956,8 @@ int vicgpu_records_wait(vicgpu_ctx* c, int k) {
   if (k < -1 || k >= R.last_nrecords) return VICGPU_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   if (k < 0) { HIPCHK(c, hipEventSynchronize(R.drained)); return VICGPU_OK; }
+  // with groups the reduction of record k is queued behind every lane's part of it, on the same stream
+  if (R.ngroup > 0) { HIPCHK(c, hipEventSynchronize(R.reduced[k])); return VICGPU_OK; }
   for (int lane = 0; lane < R.nlane; lane++) HIPCHK(c, hipEventSynchronize(R.landed[(size_t)lane * R.last_nrecords + k]));
   return VICGPU_OK;
 }
