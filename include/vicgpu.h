@@ -461,6 +461,39 @@ int vicgpu_set_retire_on_error(vicgpu_ctx *ctx, int mask);        /* OR of VICGP
 int vicgpu_set_cell_valid(vicgpu_ctx *ctx, const int *valid);     /* [ncell], 0 = skip the cell from the next step on (cell.isValid) */
 int vicgpu_get_cell_valid(vicgpu_ctx *ctx, int *valid);           /* [ncell], 1 / 0 */
 
+/* ---- model state copied between cells on the device: the ensemble workflows that move state from one member (= a block of
+ * cells) to another without a host round trip -- seeding (spin up one member, hand its state to all), resampling (a particle
+ * filter replaces members by copies of other members, every assimilation cycle) and rollback (a spare block of cells kept as
+ * a snapshot of a member, restored from later).
+ *   vicgpu_copy_cells   for every i < n, cell dst_cell[i] takes the listed rows of cell src_cell[i].  what = an OR of
+ *                       VICGPU_COPY_STATE    every SD_* / SDN_* row, every SI_* / SIN_* row and every FX_* row of the cell's HRUs
+ *                       VICGPU_COPY_BALANCE  every PB_* row of the cell (vicgpu_out.h: put_data's bookkeeping, which has no
+ *                                            setter), so that the destination's next OUT_DELSOILMOIST / OUT_WATER_ERROR continue
+ *                                            the source's instead of showing the jump; needs vicgpu_put_data_config.
+ * The assignment is simultaneous: every source is read as it was before the call, so a permutation (a rotation, a swap) is
+ * legal.  A source may repeat; a destination must not.  dst == src is a legal pair and a no-op, and so is n == 0.
+ * HRUs pair by position: the j-th HRU of the destination cell, in cell_hru_list order, takes the j-th HRU of the source cell.
+ * Values are copied verbatim, nothing is rescaled: a member with other soil depths gets the source's millimetres, exactly as
+ * vicgpu_set_state would give it.  A pair is legal only if both cells have the same number of HRUs and, position by position,
+ * equal HPI_BAND, HPI_VEG_CLASS, HPI_IS_GLACIER and HPI_IS_ARTIFICIAL_BARE.
+ * Untouched: the parameters, the forcing map and the validity table (a retired destination stays retired; its columns still
+ * take the copy), hru_err and the cell flag words, CO_* and CA_*, the un-aggregated output values and the aggregates, the
+ * records configuration and the cell groups, the forcing chunks, the finite-difference workspace.
+ * Order: the call takes effect after every step queued before it and before every step queued after it (it is queued on the
+ * context's stream, which with the finite-difference pipeline waits for every cell chunk first).  It need not have finished
+ * when it returns: vicgpu_synchronize waits for it, and so does every read-back.  Records of an earlier vicgpu_run_records that
+ * are still on their way are not affected (they read the record slots, not these tables).
+ * Two paths with identical results: when no destination is also the source of another pair (the fan-out from one member) one
+ * kernel per table copies the columns in place; otherwise the columns go through a staging buffer, the rows in passes, so
+ * that the staging memory stays within VICGPU_COPY_STAGE_MB (256; read per vicgpu_set_domain) whatever the number of pairs.
+ * Every failing call leaves every table bit-identical; all pairs are checked before the first write.
+ * VICGPU_ERR_ARG: a null handle, null lists with n > 0, n < 0, a cell outside [0, ncell), a repeated destination, `what` 0 or
+ * with unknown bits, an incompatible pair; VICGPU_ERR_STATE: no domain, VICGPU_COPY_BALANCE without a put_data configuration;
+ * VICGPU_ERR_HIP: the runtime refused an allocation -- nothing is left behind. */
+#define VICGPU_COPY_STATE   1
+#define VICGPU_COPY_BALANCE 2
+int vicgpu_copy_cells(vicgpu_ctx *ctx, int n, const int *dst_cell, const int *src_cell, int what);
+
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */
 int   vicgpu_set_write_fluxes(vicgpu_ctx *ctx, int on);           /* 0: skip the per-HRU flux table (accumulators still kept) */

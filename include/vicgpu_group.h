@@ -85,6 +85,14 @@ int vicgpu_group_get_cell_errors(vicgpu_group *g, int *flags);
 int vicgpu_group_set_retire_on_error(vicgpu_group *g, int mask);
 int vicgpu_group_set_cell_valid(vicgpu_group *g, const int *valid);
 int vicgpu_group_get_cell_valid(vicgpu_group *g, int *valid);
+/* vicgpu_copy_cells (vicgpu.h) with cell indices in the caller's global order.  The contract is the same and holds across the
+ * whole group: a pair whose cells lie in different shards is legal (the fan-out from member 0 of a sharded ensemble always
+ * has such pairs), every pair is checked before any shard writes, and every source is read before any destination is
+ * written -- per table and row pass every shard first packs what leaves its cells into an export buffer, then, once all have,
+ * fetches what it imports by plain device-to-device copies (no peer access is enabled, no kernel reads another device's
+ * memory) and unpacks it.  The call returns when the copy has been made.  Errors: as vicgpu_copy_cells, and the rule for shard
+ * failures above.  Copies between distinct devices have only been exercised as several shards on one device. */
+int vicgpu_group_copy_cells(vicgpu_group *g, int n, const int *dst_cell, const int *src_cell, int what);
 int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);

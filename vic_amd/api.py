@@ -74,6 +74,7 @@ def load_library():
         "vicgpu_get_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up]),
         "vicgpu_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
         "vicgpu_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
+        "vicgpu_copy_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, _ip, ctypes.c_int]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -117,6 +118,7 @@ def load_library():
         "vicgpu_group_swap_forcing": (ctypes.c_int, [vp]),
         "vicgpu_group_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
         "vicgpu_group_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
+        "vicgpu_group_copy_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, _ip, ctypes.c_int]),
         "vicgpu_group_step": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "vicgpu_group_synchronize": (ctypes.c_int, [vp]),
         "vicgpu_group_put_data_config": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -151,7 +153,7 @@ GROUP_ENTRIES = [
     "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
     "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
-    "set_forcing_map", "get_forcing_map",
+    "set_forcing_map", "get_forcing_map", "copy_cells",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -167,7 +169,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_records_set_groups", "vicgpu_records_get_groups", "vicgpu_records_ncol",
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
-    "vicgpu_set_forcing_map", "vicgpu_get_forcing_map",
+    "vicgpu_set_forcing_map", "vicgpu_get_forcing_map", "vicgpu_copy_cells",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -331,6 +333,18 @@ class Model:
         m = np.zeros(self.dom.ncell, dtype=np.int32)
         self._chk(self.lib.vicgpu_get_forcing_map(self.h, ctypes.byref(n), _i(m)))
         return n.value, m
+
+    # ---- model state copied between cells on the device (ensemble seeding, resampling, rollback)
+    STATE, BALANCE = C["VICGPU_COPY_STATE"], C["VICGPU_COPY_BALANCE"]
+
+    def copy_cells(self, dst, src, what=STATE):
+        """vicgpu_copy_cells: cell dst[i] takes the state (STATE: every SD / SI / FX row of its HRUs, paired by position) and /
+        or the balance bookkeeping (BALANCE: every PB row) of cell src[i]; simultaneous, so a permutation is legal; a source
+        may repeat, a destination must not.  Queued behind the steps queued so far; synchronize() waits for it."""
+        d = np.ascontiguousarray(dst, dtype=np.int32)
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        assert d.ndim == 1 and d.shape == s.shape, (d.shape, s.shape)
+        self._chk(self.lib.vicgpu_copy_cells(self.h, len(d), _i(d), _i(s), int(what)))
 
     def get_forcing(self, step):
         f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)

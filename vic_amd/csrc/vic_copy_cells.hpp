@@ -1,0 +1,201 @@
+// vic_copy_cells.hpp — model state copied between cells on the device (vicgpu_copy_cells, include/vicgpu.h): the planning of
+// a call on the host, the column-gather kernels for gfx950 and their launchers.  Nothing here knows a context: the tables are
+// [nrow][ld] arrays of double or int, the pairs are column indices.
+//
+//   plan_cell_copy     (host, no HIP) checks a call's cell pairs -- range, repeated destination, equal HRU structure position
+//                      by position -- before anything is written, drops the identity pairs and turns the rest into cell
+//                      pairs (for the per-cell tables) and HRU pairs (the j-th HRU of the destination cell, in CSR order,
+//                      takes the j-th of the source cell), both sorted by destination: consecutive lanes then write
+//                      consecutive columns where destination cells are contiguous (member-major ensembles).  It also says
+//                      whether the direct path is legal: no destination is the source of another remaining pair.
+//   vic_copy_direct    T[r][dst_j] = T[r][src_j]: one kernel per table.  Legal on the direct path only -- a lane then reads
+//                      columns no lane writes.
+//   vic_copy_pack      stage[r][j] = T[r][src_j]
+//   vic_copy_unpack    T[r][dst_j] = stage[r][j]: the staged path, for permutations (every source is read as it was before
+//                      the call).  The rows go in passes of at most `rows_per_pass` rows, so the stage never exceeds a budget
+//                      (copy_rows_per_pass); the passes are independent, because a row is read and written within its own pass.
+// Geometry of vic_out_group_reduce: a lane is one pair and a tile of CC_ROWS rows (blockIdx.y); the two indices are loaded once
+// and reused for the tile's rows; a tile's loads are all issued before its stores.  One template over the element type.  No
+// LDS, no scratch, plain vector loads and stores.  The kernels trust their indices: plan_cell_copy has checked them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <vector>
+
+namespace vic {
+
+// ------------------------------------------------------------------------------------------------ planning (host)
+enum { COPY_OK = 0, COPY_CELL_RANGE, COPY_DST_REPEATS, COPY_HRU_COUNT, COPY_HRU_STRUCTURE };
+
+struct CopyPairs {
+  std::vector<int> dst, src;       // column j of dst takes column j of src; dst ascending, no identity pair
+  size_t size() const { return dst.size(); }
+};
+struct CopyPlan {
+  int fault = COPY_OK;             // COPY_*: the first rule a pair breaks
+  int index = -1;                  // ... and the pair that breaks it
+  bool direct = true;              // no destination is also the source of a remaining pair
+  CopyPairs cell, hru;
+};
+
+// pairs (dst[i] <- src_of[dst[i]]) for every column with src_of >= 0, ascending: a scan instead of a sort
+static inline void copy_pairs_from(const std::vector<int>& src_of, size_t count, CopyPairs& out) {
+  out.dst.clear(); out.src.clear();
+  out.dst.reserve(count); out.src.reserve(count);
+  for (size_t d = 0; d < src_of.size(); d++)
+    if (src_of[d] >= 0) { out.dst.push_back((int)d); out.src.push_back(src_of[d]); }
+}
+
+// cell_off[ncell + 1] / cell_list[nhru]: the domain's CSR; key[nkey][nhru]: the HRU rows a pair must agree in, position by
+// position.  Every pair is checked before the plan holds anything.
+static inline CopyPlan plan_cell_copy(int ncell, int nhru, const int* cell_off, const int* cell_list, const int* key, int nkey, int n,
+                                      const int* dst_cell, const int* src_cell) {
+  CopyPlan p;
+  const auto fail = [&](int rule, int i) { p.fault = rule; p.index = i; return p; };
+  for (int i = 0; i < n; i++)
+    if (dst_cell[i] < 0 || dst_cell[i] >= ncell || src_cell[i] < 0 || src_cell[i] >= ncell) return fail(COPY_CELL_RANGE, i);
+  std::vector<int> src_of(ncell, -1);          // by destination cell; identity pairs count as destinations too
+  for (int i = 0; i < n; i++) {
+    if (src_of[dst_cell[i]] >= 0) return fail(COPY_DST_REPEATS, i);
+    src_of[dst_cell[i]] = src_cell[i];
+  }
+  size_t ncp = 0, nhp = 0;
+  for (int i = 0; i < n; i++) {
+    const int d = dst_cell[i], s = src_cell[i];
+    if (d == s) { src_of[d] = -1; continue; }
+    const int nh = cell_off[d + 1] - cell_off[d];
+    if (cell_off[s + 1] - cell_off[s] != nh) return fail(COPY_HRU_COUNT, i);
+    for (int j = 0; j < nh; j++) {
+      const int hd = cell_list[cell_off[d] + j], hs = cell_list[cell_off[s] + j];
+      for (int k = 0; k < nkey; k++)
+        if (key[(size_t)k * nhru + hd] != key[(size_t)k * nhru + hs]) return fail(COPY_HRU_STRUCTURE, i);
+    }
+    ncp++; nhp += nh;
+  }
+  copy_pairs_from(src_of, ncp, p.cell);
+  std::vector<char> is_dst(ncell, 0);
+  for (int d : p.cell.dst) is_dst[d] = 1;
+  for (int s : p.cell.src) if (is_dst[s]) p.direct = false;
+  std::vector<int> hsrc_of(nhru, -1);
+  for (size_t i = 0; i < p.cell.size(); i++) {
+    const int d = p.cell.dst[i], s = p.cell.src[i];
+    for (int j = 0, nh = cell_off[d + 1] - cell_off[d]; j < nh; j++) hsrc_of[cell_list[cell_off[d] + j]] = cell_list[cell_off[s] + j];
+  }
+  copy_pairs_from(hsrc_of, nhp, p.hru);
+  return p;
+}
+
+// Rows a pass of the staged path may hold: as many as fit into budget_bytes, at least one, at most all
+static inline int copy_rows_per_pass(size_t budget_bytes, size_t npair, size_t elem_bytes, int nrow) {
+  const size_t row = npair * elem_bytes;
+  const size_t fit = row ? budget_bytes / row : (size_t)nrow;
+  return fit < 1 ? 1 : (fit > (size_t)nrow ? nrow : (int)fit);
+}
+
+// ------------------------------------------------------------------------------------------------ kernels
+constexpr int CC_ROWS = 8;         // rows per launch row (blockIdx.y): values a lane holds between its loads and its stores
+
+template <typename T>
+struct CCArgs {
+  int npair, nrow;                 // pairs; rows of this launch, counted from the row `table` and `stage` point to
+  size_t ld;                       // columns per row of the table
+  const int* dst;                  // [npair] (direct, unpack)
+  const int* src;                  // [npair] (direct, pack)
+  T* table;                        // [nrow][ld]
+  T* stage;                        // [nrow][npair] (pack, unpack)
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void vic_copy_direct(const CCArgs<T> a) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= a.npair) return;
+  const int r0 = blockIdx.y * CC_ROWS;
+  const T* in = a.table + (size_t)r0 * a.ld + a.src[j];
+  T* out = a.table + (size_t)r0 * a.ld + a.dst[j];
+  T v[CC_ROWS];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.ld];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) out[(size_t)i * a.ld] = v[i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void vic_copy_pack(const CCArgs<T> a) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= a.npair) return;
+  const int r0 = blockIdx.y * CC_ROWS;
+  const T* __restrict__ in = a.table + (size_t)r0 * a.ld + a.src[j];
+  T* __restrict__ out = a.stage + (size_t)r0 * a.npair + j;
+  T v[CC_ROWS];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.ld];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) out[(size_t)i * a.npair] = v[i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void vic_copy_unpack(const CCArgs<T> a) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= a.npair) return;
+  const int r0 = blockIdx.y * CC_ROWS;
+  const T* __restrict__ in = a.stage + (size_t)r0 * a.npair + j;
+  T* __restrict__ out = a.table + (size_t)r0 * a.ld + a.dst[j];
+  T v[CC_ROWS];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.npair];
+#pragma unroll
+  for (int i = 0; i < CC_ROWS; i++)
+    if (r0 + i < a.nrow) out[(size_t)i * a.ld] = v[i];
+}
+
+// ------------------------------------------------------------------------------------------------ launchers (host)
+static inline dim3 copy_grid(int npair, int nrow) { return dim3((unsigned)((npair + 63) / 64), (unsigned)((nrow + CC_ROWS - 1) / CC_ROWS)); }
+
+// every row of table[nrow][ld] on the direct path; d_dst / d_src: the pairs in device memory
+template <typename T>
+static inline hipError_t copy_direct(hipStream_t st, T* table, size_t ld, int nrow, const int* d_dst, const int* d_src, int npair) {
+  if (npair <= 0 || nrow <= 0) return hipSuccess;
+  CCArgs<T> a;
+  a.npair = npair; a.nrow = nrow; a.ld = ld; a.dst = d_dst; a.src = d_src; a.table = table; a.stage = nullptr;
+  hipLaunchKernelGGL((vic_copy_direct<T>), copy_grid(npair, nrow), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+// rows [r0, r0 + nr) of table[..][ld]: the columns d_src[0 .. npair) into stage[nr][npair]
+template <typename T>
+static inline hipError_t copy_pack(hipStream_t st, const T* table, size_t ld, int r0, int nr, const int* d_src, int npair, T* stage) {
+  if (npair <= 0 || nr <= 0) return hipSuccess;
+  CCArgs<T> a;
+  a.npair = npair; a.nrow = nr; a.ld = ld; a.dst = nullptr; a.src = d_src; a.table = const_cast<T*>(table) + (size_t)r0 * ld; a.stage = stage;
+  hipLaunchKernelGGL((vic_copy_pack<T>), copy_grid(npair, nr), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+// ... and stage[nr][npair] into the columns d_dst[0 .. npair) of those rows
+template <typename T>
+static inline hipError_t copy_unpack(hipStream_t st, T* table, size_t ld, int r0, int nr, const int* d_dst, int npair, const T* stage) {
+  if (npair <= 0 || nr <= 0) return hipSuccess;
+  CCArgs<T> a;
+  a.npair = npair; a.nrow = nr; a.ld = ld; a.dst = d_dst; a.src = nullptr; a.table = table + (size_t)r0 * ld; a.stage = const_cast<T*>(stage);
+  hipLaunchKernelGGL((vic_copy_unpack<T>), copy_grid(npair, nr), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+// every row of table[nrow][ld] on the staged path, rows_per_pass rows at a time through stage[rows_per_pass][npair]
+template <typename T>
+static inline hipError_t copy_staged(hipStream_t st, T* table, size_t ld, int nrow, const int* d_dst, const int* d_src, int npair, T* stage,
+                                     int rows_per_pass) {
+  hipError_t e = hipSuccess;
+  for (int r0 = 0; r0 < nrow && e == hipSuccess; r0 += rows_per_pass) {
+    const int nr = nrow - r0 < rows_per_pass ? nrow - r0 : rows_per_pass;
+    if ((e = copy_pack(st, table, ld, r0, nr, d_src, npair, stage)) == hipSuccess) e = copy_unpack(st, table, ld, r0, nr, d_dst, npair, stage);
+  }
+  return e;
+}
+
+}  // namespace vic

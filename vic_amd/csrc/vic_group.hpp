@@ -90,6 +90,9 @@ struct vicgpu_group {
   // on that its cells span, its own map rebased by col_lo[k].  Identity: ncol == ncell, cell_col empty, col_lo[k] == bounds[k]
   int ncol = 0;
   std::vector<int> cell_col, col_lo;
+  // for vicgpu_group_copy_cells, which plans on the whole domain: the caller's CSR lists, the HRU rows a pair of cells must
+  // agree in ([COPY_NKEY][nhru]), and every HRU's shard and id within it
+  std::vector<int> cell_off, cell_list, copy_key, hru_shard, hru_local;
   int nshard() const { return (int)ctx.size(); }
   int c0(int k) const { return bounds[k]; }
   void identity_map() { ncol = ncell; cell_col.clear(); col_lo.assign(bounds.begin(), bounds.end() - 1); }
@@ -267,6 +270,14 @@ int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* 
   }
   g->rec_first.resize(ns);
   for (int k = 0; k < ns; k++) g->rec_first[k] = off[b[k]];
+  g->cell_off.assign(off, off + ncell + 1);
+  g->cell_list.assign(list, list + nhru);
+  g->copy_key.resize((size_t)COPY_NKEY * nhru);
+  for (int r = 0; r < COPY_NKEY; r++)
+    std::copy(hpi + (size_t)COPY_KEY_ROWS[r] * nhru, hpi + (size_t)(COPY_KEY_ROWS[r] + 1) * nhru, g->copy_key.begin() + (size_t)r * nhru);
+  g->hru_local = new_id;
+  g->hru_shard.resize(nhru);
+  for (int h = 0; h < nhru; h++) g->hru_shard[h] = shard_of[hpi[(size_t)HPI_CELL * nhru + h]];
   g->identity_map();               // as every shard's vicgpu_set_domain has left it
   g->domain_ready = true;
   return VICGPU_OK;
@@ -460,6 +471,152 @@ int vicgpu_group_glacier_mass_balance_fit(vicgpu_group* g, double* eq, int reset
   if (!g || !eq) return VICGPU_ERR_ARG;
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) { return glacier_fit_impl(g->ctx[k], eq + g->c0(k), reset, g->ncell); });
+}
+
+// Model state copied between cells (vicgpu_copy_cells, vicgpu.h) in the caller's global cell order; a pair's cells may lie in
+// different shards.  The plan is made on the whole domain, so every pair is checked before any shard writes.  Per table and
+// row pass, two phases of all shards, every read before every write:
+//   1. shard k packs what leaves its cells into its export buffer, one block [rows][pairs k -> s] per destination shard s
+//      (its own staged pairs are the block k -> k), and waits for that;
+//   2. shard s fetches the blocks k -> s of the other shards into its import buffer by plain device-to-device hipMemcpyAsync
+//      (the runtime routes it between devices; no peer access is enabled, no kernel dereferences another device's memory)
+//      and unpacks them and its own block s -> s into its tables, and waits for that.
+// The row passes keep both buffers within the staging budget (VICGPU_COPY_STAGE_MB of the first shard's context).
+struct GroupCopyKind {             // the pairs of one kind of column (HRUs or cells), by shard, in shard-local ids
+  std::vector<std::vector<int>> src, dst;      // [k * ns + s]: pairs whose source is in shard k and whose destination in shard s
+  std::vector<size_t> exp_off, imp_off;        // [k * ns + s]: first pair of the block in k's export list / in s's import list
+  std::vector<size_t> exp_n, imp_n;            // [shard]: pairs it exports / imports from others
+};
+
+static void group_copy_kind(int ns, const CopyPairs& pairs, const std::vector<int>& shard, const std::vector<int>& local, GroupCopyKind& K) {
+  K.src.assign((size_t)ns * ns, std::vector<int>()); K.dst.assign((size_t)ns * ns, std::vector<int>());
+  for (size_t i = 0; i < pairs.size(); i++) {                // dst ascending, and so within every block
+    const size_t b = (size_t)shard[pairs.src[i]] * ns + shard[pairs.dst[i]];
+    K.src[b].push_back(local[pairs.src[i]]); K.dst[b].push_back(local[pairs.dst[i]]);
+  }
+  K.exp_off.assign((size_t)ns * ns, 0); K.imp_off.assign((size_t)ns * ns, 0);
+  K.exp_n.assign(ns, 0); K.imp_n.assign(ns, 0);
+  for (int k = 0; k < ns; k++)
+    for (int s = 0; s < ns; s++) {
+      const size_t b = (size_t)k * ns + s;
+      K.exp_off[b] = K.exp_n[k]; K.exp_n[k] += K.src[b].size();
+      if (k != s) { K.imp_off[b] = K.imp_n[s]; K.imp_n[s] += K.src[b].size(); }
+    }
+}
+
+int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const int* src_cell, int what) {
+  if (!g || n < 0 || (n > 0 && (!dst_cell || !src_cell))) return VICGPU_ERR_ARG;
+  if (what == 0 || (what & ~(VICGPU_COPY_STATE | VICGPU_COPY_BALANCE))) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  if (what & VICGPU_COPY_BALANCE)
+    for (vicgpu_ctx* c : g->ctx)
+      if (!c->dom.put_on) return group_fail(g, VICGPU_ERR_STATE, "copy_cells: VICGPU_COPY_BALANCE without a put_data configuration");
+  const CopyPlan p = plan_cell_copy(g->ncell, g->nhru, g->cell_off.data(), g->cell_list.data(), g->copy_key.data(), COPY_NKEY, n, dst_cell, src_cell);
+  if (p.fault != COPY_OK) return group_fail(g, VICGPU_ERR_ARG, copy_fault_text(p));
+  if (p.cell.size() == 0) return VICGPU_OK;
+  const int ns = g->nshard();
+  std::vector<int> cell_shard(g->ncell), cell_local(g->ncell);
+  for (int k = 0; k < ns; k++)
+    for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) { cell_shard[i] = k; cell_local[i] = i - g->bounds[k]; }
+  GroupCopyKind kind[2];           // [0] HRUs, [1] cells
+  group_copy_kind(ns, p.hru, g->hru_shard, g->hru_local, kind[0]);
+  group_copy_kind(ns, p.cell, cell_shard, cell_local, kind[1]);
+  // rows per pass of every table: the largest export or import list of its kind within the budget
+  const size_t budget = (size_t)g->ctx[0]->tune.copy_stage_mb << 20;
+  int rpp[COPY_NTABLE] = {0, 0, 0, 0};
+  int nrow_of[COPY_NTABLE] = {0, 0, 0, 0};
+  std::vector<size_t> exp_bytes(ns, 0), imp_bytes(ns, 0);
+  for (int t = 0; t < COPY_NTABLE; t++)
+    HIPIGN(copy_table(g->ctx[0], t, what, [&](auto* table, int nrow, size_t, bool per_cell) {
+      const GroupCopyKind& K = kind[per_cell ? 1 : 0];
+      size_t most = 0;
+      for (int k = 0; k < ns; k++) most = std::max(most, std::max(K.exp_n[k], K.imp_n[k]));
+      rpp[t] = copy_rows_per_pass(budget, most, sizeof(*table), nrow);
+      nrow_of[t] = nrow;
+      for (int k = 0; k < ns; k++) {
+        exp_bytes[k] = std::max(exp_bytes[k], (size_t)rpp[t] * K.exp_n[k] * sizeof(*table));
+        imp_bytes[k] = std::max(imp_bytes[k], (size_t)rpp[t] * K.imp_n[k] * sizeof(*table));
+      }
+      return hipSuccess;
+    }));
+  // phase 0: every shard allocates what it needs and uploads its lists; nothing has been written when one of them is refused.
+  // A shard's list: per kind, the sources of its export blocks, then the destinations of the blocks it unpacks (k -> s by k).
+  std::vector<DevBuf<int>> idx(ns);
+  std::vector<DevBuf<double>> exp_buf(ns), imp_buf(ns);
+  std::vector<size_t> dst_at((size_t)2 * ns * ns, 0), src_at((size_t)2 * ns, 0);      // [kind][k][s] / [kind][shard]: position in the shard's list
+  int r = group_each(g, [&](int s) {
+    vicgpu_ctx* c = g->ctx[s];
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int> h;
+    for (int q = 0; q < 2; q++) {
+      const GroupCopyKind& K = kind[q];
+      src_at[(size_t)q * ns + s] = h.size();
+      for (int to = 0; to < ns; to++) h.insert(h.end(), K.src[(size_t)s * ns + to].begin(), K.src[(size_t)s * ns + to].end());
+      for (int k = 0; k < ns; k++) {
+        dst_at[((size_t)q * ns + k) * ns + s] = h.size();
+        h.insert(h.end(), K.dst[(size_t)k * ns + s].begin(), K.dst[(size_t)k * ns + s].end());
+      }
+    }
+    if (h.empty()) return (int)VICGPU_OK;
+    HIPCHK(c, idx[s].alloc(h.size()));
+    if (exp_bytes[s]) HIPCHK(c, exp_buf[s].alloc((exp_bytes[s] + 7) / 8));
+    if (imp_bytes[s]) HIPCHK(c, imp_buf[s].alloc((imp_bytes[s] + 7) / 8));
+    HIPCHK(c, idx[s].upload(c->stream, h.data()));       // waits for the steps queued so far
+    return (int)VICGPU_OK;
+  });
+  for (int t = 0; t < COPY_NTABLE && r == VICGPU_OK; t++)
+    for (int r0 = 0; r0 < nrow_of[t] && r == VICGPU_OK; r0 += rpp[t]) {
+      const int nr = std::min(rpp[t], nrow_of[t] - r0);
+      const size_t cap = rpp[t];                       // rows a block is laid out for
+      r = group_each(g, [&](int k) {                   // 1. pack
+        vicgpu_ctx* c = g->ctx[k];
+        HIPCHK(c, hipSetDevice(c->device));
+        const hipError_t packed = copy_table(c, t, what, [&](auto* table, int, size_t ld, bool per_cell) {
+          using T = typename std::remove_pointer<decltype(table)>::type;
+          const int q = per_cell ? 1 : 0;
+          const GroupCopyKind& K = kind[q];
+          hipError_t e = hipSuccess;
+          for (int s = 0; s < ns && e == hipSuccess; s++) {
+            const size_t b = (size_t)k * ns + s;
+            e = copy_pack<T>(c->stream, table, ld, r0, nr, idx[k].get() + src_at[(size_t)q * ns + k] + K.exp_off[b], (int)K.src[b].size(),
+                             reinterpret_cast<T*>(exp_buf[k].get()) + cap * K.exp_off[b]);
+          }
+          return e;
+        });
+        HIPCHK(c, packed);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return (int)VICGPU_OK;
+      });
+      if (r != VICGPU_OK) break;
+      r = group_each(g, [&](int s) {                   // 2. fetch and unpack
+        vicgpu_ctx* c = g->ctx[s];
+        HIPCHK(c, hipSetDevice(c->device));
+        const hipError_t unpacked = copy_table(c, t, what, [&](auto* table, int, size_t ld, bool per_cell) {
+          using T = typename std::remove_pointer<decltype(table)>::type;
+          const int q = per_cell ? 1 : 0;
+          const GroupCopyKind& K = kind[q];
+          hipError_t e = hipSuccess;
+          for (int k = 0; k < ns && e == hipSuccess; k++) {
+            const size_t b = (size_t)k * ns + s, np = K.src[b].size();
+            if (np == 0) continue;
+            const T* block = reinterpret_cast<const T*>(exp_buf[k].get()) + cap * K.exp_off[b];
+            if (k != s) {
+              T* mine = reinterpret_cast<T*>(imp_buf[s].get()) + cap * K.imp_off[b];
+              e = hipMemcpyAsync(mine, block, sizeof(T) * nr * np, hipMemcpyDeviceToDevice, c->stream);
+              block = mine;
+            }
+            if (e == hipSuccess) e = copy_unpack<T>(c->stream, table, ld, r0, nr, idx[s].get() + dst_at[((size_t)q * ns + k) * ns + s], (int)np, block);
+          }
+          return e;
+        });
+        HIPCHK(c, unpacked);
+        HIPCHK(c, hipStreamSynchronize(c->stream));    // the next pass packs into the buffers the others have just read
+        return (int)VICGPU_OK;
+      });
+    }
+  if (r != VICGPU_OK)              // a shard's stream may still hold kernels on the buffers that go now
+    for (vicgpu_ctx* c : g->ctx) vicgpu_synchronize(c);
+  return r;
 }
 
 // Output records (vicgpu_out.h): every shard packs its own records and copies its columns into the caller's global tables

@@ -25,6 +25,7 @@
 #include "vic_kernels.hpp"
 #include "vic_aux_kernels.hpp"
 #include "vic_records.hpp"
+#include "vic_copy_cells.hpp"
 
 using namespace vic;
 
@@ -84,6 +85,9 @@ struct Domain {
   std::vector<int> cell_col;       // empty: identity
   DevBuf<int> d_cell_col;          // [ncell]
   DevBuf<int> d_hru_fcol;          // [nhru]
+  // host copies for vicgpu_copy_cells, which plans on the host: the CSR lists and the HRU rows a pair of cells must agree in
+  // (COPY_KEY_ROWS), [COPY_NKEY][nhru]
+  std::vector<int> cell_off, cell_list, copy_key;
   // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
   bool fd = false;
   DevBuf<unsigned long long> d_ctx;
@@ -99,6 +103,10 @@ struct Domain {
   DevBuf<unsigned char> d_rowagg;  // [out_nrow] aggregation type of every output row
 };
 
+// the HRU parameter rows in which the cells of a vicgpu_copy_cells pair must agree, position by position
+constexpr int COPY_NKEY = 4;
+constexpr int COPY_KEY_ROWS[COPY_NKEY] = {HPI_BAND, HPI_VEG_CLASS, HPI_IS_GLACIER, HPI_IS_ARTIFICIAL_BARE};
+
 // The tuning variables of the environment: overrides for A/B runs, profiles and traces, not API (table in DESIGN.md (d)).
 // Read once per vicgpu_set_domain, so a domain runs on what the environment said when it was set, and a second
 // vicgpu_set_domain starts from the defaults again.
@@ -111,6 +119,7 @@ struct Tuning {
   bool trace_rounds = false;       // VICGPU_TRACE_ROUNDS (set): what every round leaves pending (a host round trip per round)
   bool trace = false;              // VICGPU_TRACE (set): per-step wall time and Brent rounds (a wait per step)
   bool stats = false;              // VICGPU_STATS (set): Brent rounds per step of every chunk, printed by vicgpu_destroy; the record groups' reduce time
+  int copy_stage_mb = 256;         // VICGPU_COPY_STAGE_MB, 0..65536: staging memory of a vicgpu_copy_cells call on the staged path; 0 = one row per pass
 };
 static Tuning read_tuning(int node_solver, int ncell) {
   Tuning t;
@@ -141,6 +150,11 @@ static Tuning read_tuning(int node_solver, int ncell) {
   t.trace_rounds = getenv("VICGPU_TRACE_ROUNDS") != nullptr;
   t.trace = getenv("VICGPU_TRACE") != nullptr;
   t.stats = getenv("VICGPU_STATS") != nullptr;
+  // vicgpu_copy_cells, staged path: the rows of a table go through the stage in passes that fit this budget (at least a row)
+  if (const char* ev = getenv("VICGPU_COPY_STAGE_MB")) {
+    const int mb = atoi(ev);
+    if (mb >= 0 && mb <= 65536) t.copy_stage_mb = mb;
+  }
   return t;
 }
 
@@ -701,6 +715,10 @@ static int domain_tables(vicgpu_ctx* c, const double* cell_params, const int* hp
   HIPCHK(c, d.d_cell_off.upload(st, cell_hru_offset));
   HIPCHK(c, d.d_cell_list.alloc(nhru));
   HIPCHK(c, d.d_cell_list.upload(st, cell_hru_list));
+  d.cell_off.assign(cell_hru_offset, cell_hru_offset + ncell + 1);
+  d.cell_list.assign(cell_hru_list, cell_hru_list + nhru);
+  d.copy_key.resize(COPY_NKEY * nhru);
+  for (int k = 0; k < COPY_NKEY; k++) std::copy(hpi + COPY_KEY_ROWS[k] * nhru, hpi + (COPY_KEY_ROWS[k] + 1) * nhru, d.copy_key.begin() + k * nhru);
   HIPCHK(c, d.d_sd.alloc_fill(VICGPU_SD_NROW(Nn) * nhru, 0, st));
   HIPCHK(c, d.d_si.alloc_fill(VICGPU_SI_NROW(Nn) * nhru, 0, st));
   HIPCHK(c, d.d_flux.alloc_fill(FX_NROW * nhru, 0, st));
@@ -784,6 +802,31 @@ static int domain_chunks(vicgpu_ctx* c, const int* hpi, const int* cell_hru_offs
     for (Event& e : ch.readback) HIPCHK(c, e.create(hipEventDisableTiming));
   }
   return VICGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ vicgpu_copy_cells
+// The tables a copy moves, in a fixed order: f(table, rows, columns per row, per_cell) for table t when `what` asks for it.
+// per_cell: the columns are cells (the cell pairs of the plan), else HRUs.  f is generic over the element type.
+constexpr int COPY_NTABLE = 4;
+template <typename F>
+static hipError_t copy_table(vicgpu_ctx* c, int t, int what, F&& f) {
+  Domain& d = c->dom;
+  const int Nn = c->opt.Nnode;
+  const bool state = (what & VICGPU_COPY_STATE) != 0, balance = (what & VICGPU_COPY_BALANCE) != 0;
+  switch (t) {
+    case 0: return state ? f(d.d_sd.get(), (int)VICGPU_SD_NROW(Nn), (size_t)d.nhru, false) : hipSuccess;
+    case 1: return state ? f(d.d_si.get(), (int)VICGPU_SI_NROW(Nn), (size_t)d.nhru, false) : hipSuccess;
+    case 2: return state ? f(d.d_flux.get(), (int)FX_NROW, (size_t)d.nhru, false) : hipSuccess;
+    default: return balance ? f(d.d_pb.get(), (int)PBX_NROW, (size_t)d.ncell, true) : hipSuccess;      // the public rows + put_data's own
+  }
+}
+
+static std::string copy_fault_text(const CopyPlan& p) {
+  const char* rule = p.fault == COPY_CELL_RANGE ? "a cell is outside the domain"
+                     : p.fault == COPY_DST_REPEATS ? "the destination repeats"
+                     : p.fault == COPY_HRU_COUNT ? "the cells differ in their number of HRUs"
+                                                 : "the cells' HRUs differ in band, vegetation class, glacier or bare-soil flag";
+  return "copy_cells: pair " + std::to_string(p.index) + ": " + rule;
 }
 
 // ------------------------------------------------------------------------------------------------ read-backs

@@ -9,6 +9,7 @@
 //   vic_aux_kernels.hpp  glacier fit, derived cell rows, test hooks, vic_cell_reduce, state records, forcing derivation
 //   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records); vic_out_group_reduce: its
 //                        reduction over cell groups (vicgpu_records_set_groups)
+//   vic_copy_cells.hpp   vicgpu_copy_cells: the host planning of a copy between cells, vic_copy_direct / _pack / _unpack
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -39,6 +40,7 @@
 #include "vic_kernels.hpp"
 #include "vic_aux_kernels.hpp"
 #include "vic_records.hpp"
+#include "vic_copy_cells.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -789,6 +791,66 @@ int vicgpu_set_fluxes(vicgpu_ctx* c, const double* flux) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, c->dom.d_flux.upload(c->stream, flux));
+  return VICGPU_OK;
+}
+
+// ---- model state copied between cells on the device (vic_copy_cells.hpp): ensemble seeding, resampling, rollback
+int vicgpu_copy_cells(vicgpu_ctx* c, int n, const int* dst_cell, const int* src_cell, int what) {
+  if (!c || n < 0 || (n > 0 && (!dst_cell || !src_cell))) return VICGPU_ERR_ARG;
+  if (what == 0 || (what & ~(VICGPU_COPY_STATE | VICGPU_COPY_BALANCE))) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if ((what & VICGPU_COPY_BALANCE) && !c->dom.put_on) return VICGPU_ERR_STATE;
+  const Domain& d = c->dom;
+  // every pair is checked here, before the first write
+  const CopyPlan p = plan_cell_copy(d.ncell, d.nhru, d.cell_off.data(), d.cell_list.data(), d.copy_key.data(), COPY_NKEY, n, dst_cell, src_cell);
+  if (p.fault != COPY_OK) { c->err = copy_fault_text(p); return VICGPU_ERR_ARG; }
+  if (p.cell.size() == 0) return VICGPU_OK;        // n == 0, or identity pairs only
+  HIPCHK(c, hipSetDevice(c->device));
+  const int nh = (int)p.hru.size(), nc = (int)p.cell.size();
+  // what the call allocates, before anything is queued: the pairs [HRU dst][HRU src][cell dst][cell src], and the stage
+  DevBuf<int> idx;
+  DevBuf<double> stage;
+  HIPCHK(c, idx.alloc(2 * ((size_t)nh + nc)));
+  const size_t budget = (size_t)c->tune.copy_stage_mb << 20;
+  if (!p.direct) {
+    size_t bytes = 0;
+    for (int t = 0; t < COPY_NTABLE; t++)
+      HIPIGN(copy_table(c, t, what, [&](auto* table, int nrow, size_t, bool per_cell) {
+        const size_t np = per_cell ? nc : nh, eb = sizeof(*table);
+        bytes = std::max(bytes, (size_t)copy_rows_per_pass(budget, np, eb, nrow) * np * eb);
+        return hipSuccess;
+      }));
+    HIPCHK(c, stage.alloc((bytes + 7) / 8));
+  }
+  std::vector<int> h;
+  h.reserve(idx.size());
+  h.insert(h.end(), p.hru.dst.begin(), p.hru.dst.end()); h.insert(h.end(), p.hru.src.begin(), p.hru.src.end());
+  h.insert(h.end(), p.cell.dst.begin(), p.cell.dst.end()); h.insert(h.end(), p.cell.src.begin(), p.cell.src.end());
+  // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
+  // `done` event, step_impl) and precedes every step queued later: the copy is queued there
+  Event t0, t1;                    // tuning (VICGPU_STATS): the kernels' own time
+  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  HIPCHK(c, idx.upload(c->stream, h.data()));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  size_t moved = 0;                // bytes the tables take
+  for (int t = 0; t < COPY_NTABLE; t++) {
+    const hipError_t queued = copy_table(c, t, what, [&](auto* table, int nrow, size_t ld, bool per_cell) {
+      using T = typename std::remove_pointer<decltype(table)>::type;
+      const int np = per_cell ? nc : nh;
+      const int* dst = idx.get() + (per_cell ? 2 * (size_t)nh : 0);
+      const int* src = dst + np;
+      moved += sizeof(T) * nrow * np;
+      if (p.direct) return copy_direct<T>(c->stream, table, ld, nrow, dst, src, np);
+      return copy_staged<T>(c->stream, table, ld, nrow, dst, src, np, reinterpret_cast<T*>(stage.get()), copy_rows_per_pass(budget, np, sizeof(T), nrow));
+    });
+    HIPCHK(c, queued);
+  }
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the pairs and the stage are released when the call returns
+  float ms = 0;
+  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] copy_cells: %d cell pairs, %d HRU pairs, %s, %zu bytes written: %.4f ms on the device\n", nc, nh,
+            p.direct ? "direct" : "staged", moved, ms);
   return VICGPU_OK;
 }
 
