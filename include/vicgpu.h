@@ -494,6 +494,48 @@ int vicgpu_get_cell_valid(vicgpu_ctx *ctx, int *valid);           /* [ncell], 1 
 #define VICGPU_COPY_BALANCE 2
 int vicgpu_copy_cells(vicgpu_ctx *ctx, int n, const int *dst_cell, const int *src_cell, int what);
 
+/* ---- cell and HRU parameters updated in place: the step of an ensemble loop in which the members get new parameter values
+ * -- a calibration generation changes a handful of soil rows of every member, a sensitivity sweep one row, a coupled glacier
+ * model the HPD_CV of the HRUs and CPB_AREAFRACT / CPB_BANDELEV of the bands once per coupling interval -- without the
+ * teardown of vicgpu_set_domain.
+ *   vicgpu_update_cell_params   for every k < nrow and i < n, row rows[k] of cell cells[i] of the cell parameter table takes
+ *                               values[k * n + i].  rows: rows of the caller's table, each in [0, VICGPU_CP_NROW(Nnode, Nband)).
+ *                               cells == NULL is the dense form: n must be ncell, and column i is cell i.
+ *   vicgpu_update_hru_params    the same on the HPD_* rows of the HRU columns hrus[i]; hrus == NULL: n must be nhru.
+ *   vicgpu_get_cell_params      the caller's rows [VICGPU_CP_NROW][ncell] as the library holds them
+ *   vicgpu_get_hru_params       [HPD_NROW][nhru]
+ * After the call the context is, in every table and in every later result, bit for bit the context vicgpu_set_domain would
+ * have built from the updated tables, holding everything else the current context holds.  The listed entries take the new
+ * values verbatim, and the library re-derives the rows it appends to its own copy of the table: the soil-conductivity layer
+ * constants of every listed cell and, when put_data is configured, the tree-line adjustment factors of every listed cell and
+ * of every cell that owns a listed HRU (a later vicgpu_put_data_config derives them for all cells anyway).
+ * Untouched: state and fluxes, hru_err and the cell flag words, CO_* and CA_*, PB_*, the un-aggregated output values and the
+ * aggregates, the validity table, the forcing map and both forcing chunks, the put_data and records configuration and the
+ * cell groups, the finite-difference workspace and the cell chunks, the HPI_* rows (the structure of a domain is not
+ * updatable) and the vegetation library.
+ * What follows from that, and is the driver's to handle:
+ *   - forcing chunks already uploaded keep the derived rows and the snowflag they were derived with: after a change of
+ *     CP_MAX_SNOW_TEMP, CP_MIN_RAIN_TEMP, a CPB_TFACTOR / CPB_PFACTOR or the elevation, push the forcing again;
+ *   - rows that the reference's readers derive from other rows are the caller's to keep consistent, exactly as with
+ *     vicgpu_set_domain: CPL_MAX_MOIST from depth and porosity, the node CPN_ALPHA / CPN_BETA / CPN_GAMMA, the zwtvmoist curves;
+ *   - nothing is rescaled: after an HPD_CV or depth change the state keeps its millimetres, and OUT_DELSOILMOIST /
+ *     OUT_WATER_ERROR of the next record show the jump unless vicgpu_put_data_init is called again.
+ * Order: the update takes effect after every step queued before it and before every step queued after it (it is queued on the
+ * context's stream, which with the finite-difference pipeline waits for every cell chunk first).  The caller's buffers may be
+ * reused when the call returns; vicgpu_synchronize and every read-back wait for the update.  Records of an earlier
+ * vicgpu_run_records that are still on their way are not affected.
+ * The values travel through a staging buffer on the device, the rows in passes, so that the staging memory stays within
+ * VICGPU_COPY_STAGE_MB whatever the size of the update; the result does not depend on the budget.
+ * nrow == 0 and n == 0 are legal and change nothing.  Every failing call leaves every table bit-identical; everything is
+ * checked before the first write.
+ * VICGPU_ERR_ARG: a null handle, nrow < 0 or n < 0, null rows or values with work to do, a row out of range or listed twice, a
+ * cell / HRU out of range or listed twice, a NULL list with n other than ncell / nhru; VICGPU_ERR_STATE: no domain;
+ * VICGPU_ERR_HIP: the runtime refused an allocation -- nothing is left behind. */
+int vicgpu_update_cell_params(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *cells, const double *values);
+int vicgpu_update_hru_params(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, const double *values);
+int vicgpu_get_cell_params(vicgpu_ctx *ctx, double *cell_params);  /* [VICGPU_CP_NROW][ncell] */
+int vicgpu_get_hru_params(vicgpu_ctx *ctx, double *hru_dparams);   /* [HPD_NROW][nhru] */
+
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */
 int   vicgpu_set_write_fluxes(vicgpu_ctx *ctx, int on);           /* 0: skip the per-HRU flux table (accumulators still kept) */

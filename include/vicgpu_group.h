@@ -93,6 +93,15 @@ int vicgpu_group_get_cell_valid(vicgpu_group *g, int *valid);
  * memory) and unpacks it.  The call returns when the copy has been made.  Errors: as vicgpu_copy_cells, and the rule for shard
  * failures above.  Copies between distinct devices have only been exercised as several shards on one device. */
 int vicgpu_group_copy_cells(vicgpu_group *g, int n, const int *dst_cell, const int *src_cell, int what);
+/* vicgpu_update_cell_params / vicgpu_update_hru_params (vicgpu.h) with cell / HRU indices in the caller's global order, and
+ * the getters in the caller's global layout.  The contract is the same: the whole call is checked on the whole domain before
+ * any shard writes; then every shard takes its own columns, rebased, on the group's threads.  The dense form (a NULL list)
+ * needs n == ncell / nhru of the whole domain.  Errors: as the context entries, and the rule for shard failures above -- a
+ * shard whose allocation the runtime refuses (VICGPU_ERR_HIP) is itself unchanged, the others have taken their columns. */
+int vicgpu_group_update_cell_params(vicgpu_group *g, int nrow, const int *rows, int n, const int *cells, const double *values);
+int vicgpu_group_update_hru_params(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, const double *values);
+int vicgpu_group_get_cell_params(vicgpu_group *g, double *cell_params);
+int vicgpu_group_get_hru_params(vicgpu_group *g, double *hru_dparams);
 int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);

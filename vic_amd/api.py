@@ -75,6 +75,10 @@ def load_library():
         "vicgpu_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
         "vicgpu_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
         "vicgpu_copy_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, _ip, ctypes.c_int]),
+        "vicgpu_update_cell_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_update_hru_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_get_cell_params": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_get_hru_params": (ctypes.c_int, [vp, _dp]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -119,6 +123,10 @@ def load_library():
         "vicgpu_group_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
         "vicgpu_group_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
         "vicgpu_group_copy_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, _ip, ctypes.c_int]),
+        "vicgpu_group_update_cell_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_group_update_hru_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_group_get_cell_params": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_get_hru_params": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_step": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "vicgpu_group_synchronize": (ctypes.c_int, [vp]),
         "vicgpu_group_put_data_config": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -153,7 +161,7 @@ GROUP_ENTRIES = [
     "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
     "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
-    "set_forcing_map", "get_forcing_map", "copy_cells",
+    "set_forcing_map", "get_forcing_map", "copy_cells", "update_cell_params", "update_hru_params", "get_cell_params", "get_hru_params",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -170,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
     "vicgpu_set_forcing_map", "vicgpu_get_forcing_map", "vicgpu_copy_cells",
+    "vicgpu_update_cell_params", "vicgpu_update_hru_params", "vicgpu_get_cell_params", "vicgpu_get_hru_params",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -345,6 +354,41 @@ class Model:
         s = np.ascontiguousarray(src, dtype=np.int32)
         assert d.ndim == 1 and d.shape == s.shape, (d.shape, s.shape)
         self._chk(self.lib.vicgpu_copy_cells(self.h, len(d), _i(d), _i(s), int(what)))
+
+    # ---- cell and HRU parameters updated in place (calibration generations, sensitivity sweeps, glacier coupling)
+    def _update_params(self, fn, table, rows, values, cols):
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        n = table.shape[1] if c is None else len(c)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        assert r.ndim == 1 and (c is None or c.ndim == 1) and v.shape == (len(r), n), (r.shape, v.shape, n)
+        self._chk(fn(self.h, len(r), _i(r), n, None if c is None else _i(c), _d(v)))
+        if r.size and n:             # the host tables follow only a call that got through
+            if c is None:
+                table[r] = v
+            else:
+                table[np.ix_(r, c)] = v
+
+    def update_cell_params(self, rows, values, cells=None):
+        """vicgpu_update_cell_params: values[k][i] -> row rows[k] of cell cells[i] (cells None: every cell, in order) of the
+        cell parameter table, in place; the library re-derives its own rows for the listed cells.  State, forcing, put_data,
+        records and groups stay.  Queued behind the steps queued so far.  `dom.cell_params` of this model follows."""
+        self._update_params(self.lib.vicgpu_update_cell_params, self.dom.cell_params, rows, values, cells)
+
+    def update_hru_params(self, rows, values, hrus=None):
+        """vicgpu_update_hru_params: the same on the HPD_* rows of the HRU columns `hrus`.  `dom.hru_dparams` follows."""
+        self._update_params(self.lib.vicgpu_update_hru_params, self.dom.hru_dparams, rows, values, hrus)
+
+    def get_cell_params(self):
+        """[cp_nrow][ncell]: the caller's rows of the cell parameter table as the library holds them."""
+        cp = np.zeros((abi.cp_nrow(self.opt.Nnode, self.opt.Nband), self.dom.ncell))
+        self._chk(self.lib.vicgpu_get_cell_params(self.h, _d(cp)))
+        return cp
+
+    def get_hru_params(self):
+        hpd = np.zeros((C["HPD_NROW"], self.dom.nhru))
+        self._chk(self.lib.vicgpu_get_hru_params(self.h, _d(hpd)))
+        return hpd
 
     def get_forcing(self, step):
         f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)

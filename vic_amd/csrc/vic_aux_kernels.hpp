@@ -94,9 +94,10 @@ __global__ __launch_bounds__(64) void vic_glacier_fit(const GArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ derived cell rows
-__global__ __launch_bounds__(256) void vic_derive_cell_params(double* cp, int ncell, int Nn, int Nb) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncell) return;
+// The rows the library appends to its copy of the cell parameter table (vic_types.hpp), for one cell.  Device functions: the
+// full-domain kernels below (vicgpu_set_domain, vicgpu_put_data_config) and the listed-cell kernels of vic_params.hpp
+// (vicgpu_update_cell_params / vicgpu_update_hru_params) both call them, so a re-derived row holds the bits a fresh domain gets.
+VIC_DEV void derive_cell_params_of(double* cp, int ncell, int c, int Nn, int Nb) {
   CellView cv{cp, ncell, c, Nn, Nb};
 #pragma unroll
   for (int l = 0; l < VIC_NLAYER; l++) {
@@ -109,11 +110,9 @@ __global__ __launch_bounds__(256) void vic_derive_cell_params(double* cp, int nc
   }
 }
 
-// TreeAdjustFactor of put_data.c:185-208 for every band of every cell (lane = cell; once per vicgpu_set_domain)
-__global__ __launch_bounds__(64) void vic_derive_tree_adjust(double* cp, int ncell, int nhru, int Nn, int Nb, const int* cell_off, const int* cell_list,
-                                                             const int* hpi, const double* hpd, const double* veglib) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c >= ncell) return;
+// TreeAdjustFactor of put_data.c:185-208 for every band of one cell
+VIC_DEV void derive_tree_adjust_of(double* cp, int ncell, int nhru, int c, int Nn, int Nb, const int* cell_off, const int* cell_list, const int* hpi,
+                                   const double* hpd, const double* veglib) {
   for (int b = 0; b < Nb; b++) {
     double bandCv = 0;
     for (int k = cell_off[c]; k < cell_off[c + 1]; k++) {          // hruList order, like the reference's sum
@@ -124,6 +123,20 @@ __global__ __launch_bounds__(64) void vic_derive_tree_adjust(double* cp, int nce
     const bool atl = cp[(size_t)VICGPU_CP_BAND(CPB_ABOVETREELINE, b, Nn, Nb) * ncell + c] != 0.0;
     cp[(size_t)VIC_CPX_TREE_ROW(b, Nn, Nb) * ncell + c] = atl ? 1. / (1. - bandCv) : 1.;
   }
+}
+
+__global__ __launch_bounds__(256) void vic_derive_cell_params(double* cp, int ncell, int Nn, int Nb) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncell) return;
+  derive_cell_params_of(cp, ncell, c, Nn, Nb);
+}
+
+// ... for every cell (lane = cell; once per vicgpu_put_data_config)
+__global__ __launch_bounds__(64) void vic_derive_tree_adjust(double* cp, int ncell, int nhru, int Nn, int Nb, const int* cell_off, const int* cell_list,
+                                                             const int* hpi, const double* hpd, const double* veglib) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= ncell) return;
+  derive_tree_adjust_of(cp, ncell, nhru, c, Nn, Nb, cell_off, cell_list, hpi, hpd, veglib);
 }
 
 // ------------------------------------------------------------------------------------------------ test hook

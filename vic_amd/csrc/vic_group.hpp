@@ -20,6 +20,7 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
 static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld);
+static int get_cell_params_impl(vicgpu_ctx* c, double* cell_params, int ld);
 
 // One persistent host thread per shard.  run(fn) calls fn(k) on thread k for every shard and returns when all have returned.
 // Each thread selects its shard's device once at start (every library entry selects it again anyway).
@@ -617,6 +618,82 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
   if (r != VICGPU_OK)              // a shard's stream may still hold kernels on the buffers that go now
     for (vicgpu_ctx* c : g->ctx) vicgpu_synchronize(c);
   return r;
+}
+
+// Parameters updated in place (vicgpu_update_cell_params / vicgpu_update_hru_params, vicgpu.h) in the caller's global cell /
+// HRU order.  The call is checked on the whole domain, so nothing is written when any entry is refused; then every shard
+// takes its own columns, rebased, with their values gathered into a table of its own, on the group's threads.  The dense form
+// stays dense in every shard (its cells are a block of the caller's, its HRUs are numbered in the caller's order).  The
+// group keeps no host copy of the parameter tables: there is nothing else to keep in step.
+static int group_update_params(vicgpu_group* g, bool per_cell, int nrow, const int* rows, int n, const int* cols, const double* values) {
+  if (!g || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  if (nrow == 0 || n == 0) return VICGPU_OK;
+  if (!rows || !values) return group_fail(g, VICGPU_ERR_ARG, "update params: null rows or values");
+  const int table_rows = per_cell ? (int)VICGPU_CP_NROW(g->opt.Nnode, g->opt.Nband) : (int)HPD_NROW;
+  const ParamFault f = check_param_update(table_rows, per_cell ? g->ncell : g->nhru, nrow, rows, n, cols);
+  if (f.rule != PARAM_OK)
+    return group_fail(g, VICGPU_ERR_ARG, std::string(per_cell ? "update_cell_params: " : "update_hru_params: ") +
+                                             (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
+  const int ns = g->nshard();
+  // shard k: the entries of the caller's list that are its own (pos) and their ids within it (local); dense: pos only
+  std::vector<std::vector<int>> pos(ns), local(ns);
+  if (cols) {
+    std::vector<int> cell_shard;
+    if (per_cell) {
+      cell_shard.resize(g->ncell);
+      for (int k = 0; k < ns; k++)
+        for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) cell_shard[i] = k;
+    }
+    for (int i = 0; i < n; i++) {
+      const int k = per_cell ? cell_shard[cols[i]] : g->hru_shard[cols[i]];
+      pos[k].push_back(i);
+      local[k].push_back(per_cell ? cols[i] - g->bounds[k] : g->hru_local[cols[i]]);
+    }
+  } else {
+    for (int k = 0; k < ns; k++) {
+      if (per_cell) for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) pos[k].push_back(i);
+      else pos[k] = g->hru[k];
+    }
+  }
+  return group_each(g, [&](int k) {
+    const size_t nk = pos[k].size();
+    if (nk == 0) return (int)VICGPU_OK;
+    std::vector<double> v((size_t)nrow * nk);
+    for (int r = 0; r < nrow; r++) {
+      const double* src = values + (size_t)r * n;
+      double* dst = v.data() + (size_t)r * nk;
+      for (size_t j = 0; j < nk; j++) dst[j] = src[pos[k][j]];
+    }
+    const int* idx = cols ? local[k].data() : nullptr;
+    return per_cell ? vicgpu_update_cell_params(g->ctx[k], nrow, rows, (int)nk, idx, v.data())
+                    : vicgpu_update_hru_params(g->ctx[k], nrow, rows, (int)nk, idx, v.data());
+  });
+}
+
+int vicgpu_group_update_cell_params(vicgpu_group* g, int nrow, const int* rows, int n, const int* cells, const double* values) {
+  return group_update_params(g, true, nrow, rows, n, cells, values);
+}
+
+int vicgpu_group_update_hru_params(vicgpu_group* g, int nrow, const int* rows, int n, const int* hrus, const double* values) {
+  return group_update_params(g, false, nrow, rows, n, hrus, values);
+}
+
+int vicgpu_group_get_cell_params(vicgpu_group* g, double* cell_params) {
+  if (!g || !cell_params) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) { return get_cell_params_impl(g->ctx[k], cell_params + g->c0(k), g->ncell); });
+}
+
+int vicgpu_group_get_hru_params(vicgpu_group* g, double* hru_dparams) {
+  if (!g || !hru_dparams) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  return group_each(g, [&](int k) {
+    std::vector<double> p((size_t)HPD_NROW * g->hru[k].size());
+    const int r = vicgpu_get_hru_params(g->ctx[k], p.data());
+    if (r == VICGPU_OK) merge_hru_table(g, k, p, HPD_NROW, hru_dparams);
+    return r;
+  });
 }
 
 // Output records (vicgpu_out.h): every shard packs its own records and copies its columns into the caller's global tables

@@ -26,6 +26,7 @@
 #include "vic_aux_kernels.hpp"
 #include "vic_records.hpp"
 #include "vic_copy_cells.hpp"
+#include "vic_params.hpp"
 
 using namespace vic;
 

@@ -14,7 +14,7 @@
 //                       water and energy balance errors and their bookkeeping (put_data.c:549-633).
 //   vic_put_aggregate   one lane = one cell x 32 rows: temporal aggregation (put_data.c:663-685).
 // Option subset as everywhere in this library: no lakes, Ndist = 1, SPATIAL_FROST / EXCESS_ICE off, MOISTFRACT and
-// ALMA_OUTPUT off.  The tree-line adjustment factors (put_data.c:185-208) are derived once per domain (VIC_CPX_TREE_ROW).
+// ALMA_OUTPUT off.  The tree-line adjustment factors (put_data.c:185-208) are derived per put_data configuration and parameter update (VIC_CPX_TREE_ROW).
 #pragma once
 #include "vic_types.hpp"
 #include "vicgpu_out.h"
@@ -97,7 +97,7 @@ VIC_DEV PutHru put_hru(const OArgs& a, const CellView& cv, int g) {
   h.HasGlac = is_glac;
   h.overstory = a.veglib[(size_t)a.hpi[(size_t)HPI_VEG_INDEX * nh + g] * VL_NFIELD + VL_OVERSTORY] != 0.0;
   const bool atl = cv.band(CPB_ABOVETREELINE, h.band) != 0.0;
-  h.TreeAdjust = cv.s(VIC_CPX_TREE_ROW(h.band, cv.Nn, cv.Nb));                       // put_data.c:199-208, derived with the domain
+  h.TreeAdjust = cv.s(VIC_CPX_TREE_ROW(h.band, cv.Nn, cv.Nb));                       // put_data.c:199-208, derived ahead of the step
   h.run = (h.Cv > 0) && (h.ThisAreaFract > 0.) && (art_bare || (!atl || (atl && !h.overstory)));   // :289-290
   return h;
 }

@@ -137,11 +137,13 @@ struct VegLib {
 };
 
 // Rows the library appends to its device copy of the cell parameter table (vic_derive_cell_params, once per
-// vicgpu_set_domain): the factors of soil_conductivity (soil_conduction.c:7-105) that depend on the layer's soil only.
+// vicgpu_set_domain; again for the listed cells of a vicgpu_update_cell_params): the factors of soil_conductivity
+// (soil_conduction.c:7-105) that depend on the layer's soil only.
 enum { CPX_KDRY = 0, CPX_KSP, CPX_KWP, CPX_POROSITY, CPX_NFIELD };
 #define VIC_CPX_ROW(f, l, Nn, Nb) (VICGPU_CP_NROW(Nn, Nb) + (f) * VIC_NLAYER + (l))
 // ... and put_data's tree-line adjustment factor of every band (put_data.c:185-208: a function of the HRU areas, the
-// vegetation classes and AboveTreeLine, all fixed with the domain)
+// vegetation classes and AboveTreeLine: derived by vicgpu_put_data_config, and again for the cells a later
+// vicgpu_update_cell_params / vicgpu_update_hru_params touches)
 #define VIC_CPX_TREE_ROW(b, Nn, Nb) (VICGPU_CP_NROW(Nn, Nb) + CPX_NFIELD * VIC_NLAYER + (b))
 #define VIC_CPX_NROW(Nn, Nb) (VICGPU_CP_NROW(Nn, Nb) + CPX_NFIELD * VIC_NLAYER + (Nb))
 

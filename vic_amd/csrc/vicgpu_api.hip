@@ -10,6 +10,8 @@
 //   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records); vic_out_group_reduce: its
 //                        reduction over cell groups (vicgpu_records_set_groups)
 //   vic_copy_cells.hpp   vicgpu_copy_cells: the host planning of a copy between cells, vic_copy_direct / _pack / _unpack
+//   vic_params.hpp       vicgpu_update_cell_params / _hru_params: the host check of an update, vic_param_scatter and the
+//                        listed-cell forms of the derive kernels
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -41,6 +43,7 @@
 #include "vic_aux_kernels.hpp"
 #include "vic_records.hpp"
 #include "vic_copy_cells.hpp"
+#include "vic_params.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -852,6 +855,95 @@ int vicgpu_copy_cells(vicgpu_ctx* c, int n, const int* dst_cell, const int* src_
     fprintf(stderr, "[vicgpu] copy_cells: %d cell pairs, %d HRU pairs, %s, %zu bytes written: %.4f ms on the device\n", nc, nh,
             p.direct ? "direct" : "staged", moved, ms);
   return VICGPU_OK;
+}
+
+// ---- cell and HRU parameters updated in place (vic_params.hpp): calibration generations, sensitivity sweeps, glacier coupling
+// One call on the caller's rows of d_cp (per_cell) or on d_hpd.  Everything the call allocates is allocated before the first
+// write: one list block [rows][columns, when listed][cells whose tree-line rows are re-derived, when listed] and the stage.
+static int update_params_impl(vicgpu_ctx* c, bool per_cell, int nrow, const int* rows, int n, const int* cols, const double* values) {
+  if (!c || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if (nrow == 0 || n == 0) return VICGPU_OK;
+  if (!rows || !values) return VICGPU_ERR_ARG;
+  Domain& d = c->dom;
+  const int Nn = c->opt.Nnode, Nb = c->opt.Nband;
+  const char* name = per_cell ? "update_cell_params" : "update_hru_params";
+  const int table_rows = per_cell ? (int)VICGPU_CP_NROW(Nn, Nb) : (int)HPD_NROW;
+  const int ncol = per_cell ? d.ncell : d.nhru;
+  // every row and column is checked here, before the first write
+  const ParamFault f = check_param_update(table_rows, ncol, nrow, rows, n, cols);
+  if (f.rule != PARAM_OK) {
+    c->err = std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    return VICGPU_ERR_ARG;
+  }
+  // the cells whose tree-line rows follow: the listed cells, or the owners of the listed HRUs; with a dense call, all
+  const bool tree = d.put_on && c->d_veglib;
+  std::vector<int> owners;
+  if (!per_cell && cols && tree) owners = param_owner_cells(d.ncell, d.nhru, d.cell_off.data(), d.cell_list.data(), n, cols);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nlist = cols ? (size_t)n : 0;
+  DevBuf<int> lists;
+  DevBuf<double> stage;
+  HIPCHK(c, lists.alloc((size_t)nrow + nlist + owners.size()));
+  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
+  HIPCHK(c, stage.alloc((size_t)rpp * n));
+  std::vector<int> h(rows, rows + nrow);
+  if (cols) h.insert(h.end(), cols, cols + n);
+  h.insert(h.end(), owners.begin(), owners.end());
+  const int* d_rows = lists.get();
+  const int* d_cols = cols ? lists.get() + nrow : nullptr;
+  const int* d_owners = lists.get() + nrow + nlist;
+  // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
+  // `done` event, step_impl) and precedes every step queued later: the update is queued there
+  Event t0, t1;                    // tuning (VICGPU_STATS): the call's time on the stream, uploads of the passes included
+  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  HIPCHK(c, lists.upload(c->stream, h.data()));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  int nderived = 0;
+  if (per_cell) {
+    HIPCHK(c, param_scatter_staged(c->stream, d.d_cp, (size_t)d.ncell, d_rows, nrow, d_cols, n, values, stage, rpp));
+    HIPCHK(c, derive_cell_params_listed(c->stream, d.d_cp, d.ncell, Nn, Nb, d_cols, n));
+    if (tree)
+      HIPCHK(c, derive_tree_adjust_listed(c->stream, d.d_cp, d.ncell, d.nhru, Nn, Nb, d.d_cell_off, d.d_cell_list, d.d_hpi, d.d_hpd, c->d_veglib, d_cols, n));
+    nderived = n;
+  } else {
+    HIPCHK(c, param_scatter_staged(c->stream, d.d_hpd, (size_t)d.nhru, d_rows, nrow, d_cols, n, values, stage, rpp));
+    if (tree) {
+      nderived = cols ? (int)owners.size() : d.ncell;
+      HIPCHK(c, derive_tree_adjust_listed(c->stream, d.d_cp, d.ncell, d.nhru, Nn, Nb, d.d_cell_off, d.d_cell_list, d.d_hpi, d.d_hpd, c->d_veglib,
+                                          cols ? d_owners : nullptr, nderived));
+    }
+  }
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
+  float ms = 0;
+  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] %s: %d rows x %d %s, %s, %d passes, %zu bytes written, rows re-derived for %d cells: %.4f ms on the stream\n", name,
+            nrow, n, per_cell ? "cells" : "HRUs", cols ? "listed" : "dense", (nrow + rpp - 1) / rpp, sizeof(double) * nrow * n, nderived, ms);
+  return VICGPU_OK;
+}
+
+int vicgpu_update_cell_params(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* cells, const double* values) {
+  return update_params_impl(c, true, nrow, rows, n, cells, values);
+}
+
+int vicgpu_update_hru_params(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* hrus, const double* values) {
+  return update_params_impl(c, false, nrow, rows, n, hrus, values);
+}
+
+// the caller's rows of the cell parameter table (the library's appended rows stay inside) into a table whose rows are ld cells wide
+static int get_cell_params_impl(vicgpu_ctx* c, double* cell_params, int ld) {
+  if (!c || !cell_params) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  return d2h_cols(c, cell_params, ld, c->dom.d_cp, (int)VICGPU_CP_NROW(c->opt.Nnode, c->opt.Nband));
+}
+
+int vicgpu_get_cell_params(vicgpu_ctx* c, double* cell_params) { return get_cell_params_impl(c, cell_params, c ? c->dom.ncell : 0); }
+
+int vicgpu_get_hru_params(vicgpu_ctx* c, double* hru_dparams) {
+  if (!c || !hru_dparams) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  return d2h(c, hru_dparams, c->dom.d_hpd);
 }
 
 // ------------------------------------------------------------------------------------------------ output records (vicgpu_out.h)
