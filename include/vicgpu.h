@@ -536,6 +536,64 @@ int vicgpu_update_hru_params(vicgpu_ctx *ctx, int nrow, const int *rows, int n, 
 int vicgpu_get_cell_params(vicgpu_ctx *ctx, double *cell_params);  /* [VICGPU_CP_NROW][ncell] */
 int vicgpu_get_hru_params(vicgpu_ctx *ctx, double *hru_dparams);   /* [HPD_NROW][nhru] */
 
+/* ---- model state read and changed in place, row by row, and its dependent soil rows re-derived: the analysis update of an
+ * ensemble loop -- EnKF increments on soil moisture and SWE, direct insertion of an observed SWE, a perturbation of the node
+ * temperatures -- reads a few state rows of every member, changes them and makes the rest of the state consistent with the
+ * change, without moving the whole state through the host.  The same derive is the tail of a restart into a fresh context:
+ * vicgpu_set_state_records scatters the persisted fields, vicgpu_derive_soil_state(all HRUs, NODES | LAYERS | FRONTS) gives
+ * the rows initialize_model_state.c rebuilds after it has read a state file.
+ *   vicgpu_get_state_rows      values[k * n + i] = row rows[k] of HRU hrus[i] of the SD table, for every k < nrow and i < n.
+ *                              rows: each in [0, VICGPU_SD_NROW(Nnode)).  hrus == NULL is the dense form: n must be nhru, and
+ *                              column i is HRU i.  The list rules are those of vicgpu_update_hru_params.
+ *   vicgpu_get_state_rows_i    the same on the SI table, rows in [0, VICGPU_SI_NROW(Nnode)).
+ *   vicgpu_update_state        VICGPU_STATE_SET: the listed SD entries take values[k * n + i] verbatim (NaN is legal:
+ *                              SD_GLAC_CUM_MASS_BALANCE starts as NaN).  VICGPU_STATE_ADD: they take old + values[k * n + i],
+ *                              one rounded double-precision add.  Nothing is clamped, and no other row follows: consistency is
+ *                              vicgpu_derive_soil_state's, and the caller decides when.
+ *   vicgpu_update_state_i      SET on the SI table.
+ *   vicgpu_derive_soil_state   for every listed HRU (hrus == NULL: all, n must be nhru) the stages selected in `what` run in the
+ *                              reference's order, each on what the earlier ones left:
+ *     VICGPU_DERIVE_CAP_MOIST  per layer: moist > CPL_MAX_MOIST gives ice *= max_moist / moist, moist = max_moist; then ice >
+ *                              moist gives ice = moist.  Writes SD_MOIST0..2 and SD_ICE0..2.  With GLACIER_DYNAMICS the
+ *                              reference keeps the excess in cell.excess_moist, which no table carries: VICGPU_ERR_UNSUPPORTED.
+ *     VICGPU_DERIVE_NODES      distribute_node_moisture_properties from SDN_T and SD_MOIST0..2: the SDN_MOIST, SDN_ICE,
+ *                              SDN_KAPPA and SDN_CS blocks.  An HRU with HPD_CV <= 0, or CPB_AREAFRACT <= 0 in its band, gets
+ *                              zeros in the four blocks, and neither of the two stages below runs for it.
+ *     VICGPU_DERIVE_LAYERS     SD_ICE0..2 and SD_LAYER_T0..2 by estimate_layer_ice_content, or with QUICK_FLUX by
+ *                              estimate_layer_ice_content_quick_flux from node temperatures 0 and 1.  Where the thermal nodes
+ *                              do not reach below the bottom layer (the reference returns ERROR, soil_conduction.c:526-529)
+ *                              the layers above the failing one take their values, the failing one zeros, the ones below keep
+ *                              theirs, and VICGPU_CELLERR_NODES is OR-ed into the cell's flag word, as a step reports it
+ *                              (vicgpu_get_cell_errors; vicgpu_reset_accum clears it).  No other flag is ever set here.
+ *     VICGPU_DERIVE_FRONTS     only without QUICK_FLUX and in CP_FS_ACTIVE cells: find_0_degree_fronts gives SI_NFROST, SI_NTHAW,
+ *                              FX_FDEPTH0..2 and FX_TDEPTH0..2 (NaN where there is no front).  Otherwise those rows stay.
+ * The parameters are the context's own, the library's appended rows included: a derive after vicgpu_update_cell_params works
+ * on the updated soil.  The functions are the step's own device functions: after a step, VICGPU_DERIVE_NODES reproduces the
+ * node blocks the step left.  The cell validity table is not consulted: a listed HRU of a retired cell is updated and derived.
+ * Untouched: everything vicgpu_update_cell_params leaves untouched (but the cell flag words as described), both parameter
+ * tables, and every state and flux row that is neither listed nor produced by a selected stage.
+ * Order: as for vicgpu_update_cell_params -- behind every step queued before (every cell chunk of the finite-difference
+ * pipeline included), ahead of every step queued after.  The caller's buffers are free when a call returns; a get returns with
+ * the values in place, so it waits for everything queued before it.
+ * The values travel through a staging buffer on the device, the rows in passes within VICGPU_COPY_STAGE_MB, up and down; the
+ * result does not depend on the budget.
+ * nrow == 0 and n == 0 are legal and change nothing.  Every failing call leaves every table bit-identical; everything is
+ * checked before the first write.
+ * VICGPU_ERR_ARG: as for vicgpu_update_hru_params; a `mode` other than the two; `what` 0 or with unknown bits;
+ * VICGPU_ERR_STATE: no domain; VICGPU_ERR_UNSUPPORTED: VICGPU_DERIVE_CAP_MOIST with GLACIER_DYNAMICS; VICGPU_ERR_HIP: the
+ * runtime refused an allocation -- nothing is left behind. */
+#define VICGPU_STATE_SET 0
+#define VICGPU_STATE_ADD 1
+#define VICGPU_DERIVE_CAP_MOIST 1   /* initialize_model_state.c:397-434 */
+#define VICGPU_DERIVE_NODES     2   /* :712     distribute_node_moisture_properties */
+#define VICGPU_DERIVE_LAYERS    4   /* :728-732 estimate_layer_ice_content(_quick_flux) */
+#define VICGPU_DERIVE_FRONTS    8   /* :736-737 find_0_degree_fronts */
+int vicgpu_get_state_rows(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, double *values);
+int vicgpu_get_state_rows_i(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, int *values);
+int vicgpu_update_state(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, const double *values, int mode);
+int vicgpu_update_state_i(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, const int *values);
+int vicgpu_derive_soil_state(vicgpu_ctx *ctx, int n, const int *hrus, int what);
+
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */
 int   vicgpu_set_write_fluxes(vicgpu_ctx *ctx, int on);           /* 0: skip the per-HRU flux table (accumulators still kept) */

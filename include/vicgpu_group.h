@@ -102,6 +102,16 @@ int vicgpu_group_update_cell_params(vicgpu_group *g, int nrow, const int *rows, 
 int vicgpu_group_update_hru_params(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, const double *values);
 int vicgpu_group_get_cell_params(vicgpu_group *g, double *cell_params);
 int vicgpu_group_get_hru_params(vicgpu_group *g, double *hru_dparams);
+/* vicgpu_get_state_rows / vicgpu_update_state / vicgpu_derive_soil_state and the int forms (vicgpu.h) with HRU indices in the
+ * caller's global numbering.  The contract is the same: the whole call is checked on the whole domain before any shard writes;
+ * then every shard takes its own columns, rebased, on the group's threads, and the get forms merge into the caller's
+ * [nrow][n] buffer in list order.  The dense form needs n == nhru of the whole domain.  Errors: as the context entries, and the
+ * rule for shard failures above -- a shard whose allocation the runtime refuses is itself unchanged, the others have run. */
+int vicgpu_group_get_state_rows(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, double *values);
+int vicgpu_group_get_state_rows_i(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, int *values);
+int vicgpu_group_update_state(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, const double *values, int mode);
+int vicgpu_group_update_state_i(vicgpu_group *g, int nrow, const int *rows, int n, const int *hrus, const int *values);
+int vicgpu_group_derive_soil_state(vicgpu_group *g, int n, const int *hrus, int what);
 int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);

@@ -244,6 +244,7 @@ inline int __ffsll(long long v) { return __builtin_ffsll(v); }
 inline long long __double_as_longlong(double v) { return hostemu::from_bits<long long>(hostemu::to_bits(v)); }
 inline double __longlong_as_double(long long v) { return hostemu::from_bits<double>(hostemu::to_bits(v)); }
 template <typename T, typename U> inline T atomicAdd(T* p, U v) { return __atomic_fetch_add(p, (T)v, __ATOMIC_SEQ_CST); }
+template <typename T, typename U> inline T atomicOr(T* p, U v) { return __atomic_fetch_or(p, (T)v, __ATOMIC_SEQ_CST); }
 
 // ---- runtime API subset: everything is synchronous, streams and events are tokens ----
 inline const char* hipGetErrorString(hipError_t) { return "hostemu error"; }

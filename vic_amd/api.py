@@ -79,6 +79,11 @@ def load_library():
         "vicgpu_update_hru_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
         "vicgpu_get_cell_params": (ctypes.c_int, [vp, _dp]),
         "vicgpu_get_hru_params": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_get_state_rows": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_get_state_rows_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
+        "vicgpu_update_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp, ctypes.c_int]),
+        "vicgpu_update_state_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
+        "vicgpu_derive_soil_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -127,6 +132,11 @@ def load_library():
         "vicgpu_group_update_hru_params": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
         "vicgpu_group_get_cell_params": (ctypes.c_int, [vp, _dp]),
         "vicgpu_group_get_hru_params": (ctypes.c_int, [vp, _dp]),
+        "vicgpu_group_get_state_rows": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp]),
+        "vicgpu_group_get_state_rows_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
+        "vicgpu_group_update_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp, ctypes.c_int]),
+        "vicgpu_group_update_state_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
+        "vicgpu_group_derive_soil_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
         "vicgpu_group_step": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "vicgpu_group_synchronize": (ctypes.c_int, [vp]),
         "vicgpu_group_put_data_config": (ctypes.c_int, [vp, ctypes.c_int]),
@@ -162,6 +172,7 @@ GROUP_ENTRIES = [
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
     "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
     "set_forcing_map", "get_forcing_map", "copy_cells", "update_cell_params", "update_hru_params", "get_cell_params", "get_hru_params",
+    "get_state_rows", "get_state_rows_i", "update_state", "update_state_i", "derive_soil_state",
 ]
 
 EXPORTED_SYMBOLS = [
@@ -179,6 +190,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
     "vicgpu_set_forcing_map", "vicgpu_get_forcing_map", "vicgpu_copy_cells",
     "vicgpu_update_cell_params", "vicgpu_update_hru_params", "vicgpu_get_cell_params", "vicgpu_get_hru_params",
+    "vicgpu_get_state_rows", "vicgpu_get_state_rows_i", "vicgpu_update_state", "vicgpu_update_state_i", "vicgpu_derive_soil_state",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -389,6 +401,45 @@ class Model:
         hpd = np.zeros((C["HPD_NROW"], self.dom.nhru))
         self._chk(self.lib.vicgpu_get_hru_params(self.h, _d(hpd)))
         return hpd
+
+    # ---- model state read and changed in place, its dependent soil rows re-derived (the analysis update of an ensemble loop)
+    SET, ADD = C["VICGPU_STATE_SET"], C["VICGPU_STATE_ADD"]
+    CAP_MOIST, NODES, LAYERS, FRONTS = (C["VICGPU_DERIVE_CAP_MOIST"], C["VICGPU_DERIVE_NODES"], C["VICGPU_DERIVE_LAYERS"],
+                                        C["VICGPU_DERIVE_FRONTS"])
+
+    def _state_lists(self, rows, hrus):
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        h = None if hrus is None else np.ascontiguousarray(hrus, dtype=np.int32)
+        assert r.ndim == 1 and (h is None or h.ndim == 1), (r.shape, None if h is None else h.shape)
+        return r, h, self.dom.nhru if h is None else len(h)
+
+    def get_state_rows(self, rows, hrus=None, ints=False):
+        """vicgpu_get_state_rows(_i): [len(rows)][n] -- row rows[k] of HRU hrus[i] (hrus None: every HRU, in order) of the SD
+        table (ints: of the SI table).  Waits for everything queued before it."""
+        r, h, n = self._state_lists(rows, hrus)
+        v = np.zeros((len(r), n), dtype=np.int32 if ints else np.float64)
+        fn = self.lib.vicgpu_get_state_rows_i if ints else self.lib.vicgpu_get_state_rows
+        self._chk(fn(self.h, len(r), _i(r), n, None if h is None else _i(h), _i(v) if ints else _d(v)))
+        return v
+
+    def update_state(self, rows, values, hrus=None, mode=SET, ints=False):
+        """vicgpu_update_state (ints: vicgpu_update_state_i): values[k][i] -> row rows[k] of HRU hrus[i] of the SD (SI) table,
+        verbatim (SET) or added to what is there (ADD, SD only).  No other row follows: derive_soil_state."""
+        r, h, n = self._state_lists(rows, hrus)
+        v = np.ascontiguousarray(values, dtype=np.int32 if ints else np.float64)
+        assert v.shape == (len(r), n), (v.shape, len(r), n)
+        if ints:
+            assert mode == self.SET, "the integer table takes SET only"
+            self._chk(self.lib.vicgpu_update_state_i(self.h, len(r), _i(r), n, None if h is None else _i(h), _i(v)))
+        else:
+            self._chk(self.lib.vicgpu_update_state(self.h, len(r), _i(r), n, None if h is None else _i(h), _d(v), int(mode)))
+
+    def derive_soil_state(self, what, hrus=None):
+        """vicgpu_derive_soil_state: the stages `what` (CAP_MOIST | NODES | LAYERS | FRONTS) of the tail of
+        initialize_model_state for the HRUs `hrus` (None: all), from the state and the parameters on the device."""
+        h = None if hrus is None else np.ascontiguousarray(hrus, dtype=np.int32)
+        assert h is None or h.ndim == 1
+        self._chk(self.lib.vicgpu_derive_soil_state(self.h, self.dom.nhru if h is None else len(h), None if h is None else _i(h), int(what)))
 
     def get_forcing(self, step):
         f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)

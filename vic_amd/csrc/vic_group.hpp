@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "vicgpu_group.h"
 #include "vic_checks.hpp"
@@ -693,6 +694,101 @@ int vicgpu_group_get_hru_params(vicgpu_group* g, double* hru_dparams) {
     const int r = vicgpu_get_hru_params(g->ctx[k], p.data());
     if (r == VICGPU_OK) merge_hru_table(g, k, p, HPD_NROW, hru_dparams);
     return r;
+  });
+}
+
+// Model state rows read and changed in place, the soil rows derived from them (vicgpu_get_state_rows / vicgpu_update_state /
+// vicgpu_derive_soil_state, vicgpu.h) with HRU ids in the caller's global numbering.  The call is checked on the whole domain
+// before any shard writes; then every shard takes its own columns, rebased, on the group's threads.
+}  // extern "C": the helpers are templates
+
+struct GroupHruLists {
+  std::vector<std::vector<int>> pos, local;    // [shard]: entries of the caller's list that are its own; their ids within it (listed form only)
+};
+
+static GroupHruLists group_hru_lists(const vicgpu_group* g, int n, const int* hrus) {
+  GroupHruLists L;
+  const int ns = g->nshard();
+  L.pos.resize(ns); L.local.resize(ns);
+  if (hrus) {
+    for (int i = 0; i < n; i++) {
+      const int k = g->hru_shard[hrus[i]];
+      L.pos[k].push_back(i);
+      L.local[k].push_back(g->hru_local[hrus[i]]);
+    }
+  } else {
+    for (int k = 0; k < ns; k++) L.pos[k] = g->hru[k];
+  }
+  return L;
+}
+
+// op: ROWS_GET / ROWS_SET / ROWS_ADD of the context entries; INT: the SI table
+template <typename T>
+static int group_state_rows(vicgpu_group* g, const char* name, bool INT, int op, int nrow, const int* rows, int n, const int* hrus, T* values) {
+  if (!g || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  if (nrow == 0 || n == 0) return VICGPU_OK;
+  if (!rows || !values) return group_fail(g, VICGPU_ERR_ARG, std::string(name) + ": null rows or values");
+  const int table_rows = INT ? (int)VICGPU_SI_NROW(g->opt.Nnode) : (int)VICGPU_SD_NROW(g->opt.Nnode);
+  const ParamFault f = check_param_update(table_rows, g->nhru, nrow, rows, n, hrus);
+  if (f.rule != PARAM_OK)
+    return group_fail(g, VICGPU_ERR_ARG, std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
+  const GroupHruLists L = group_hru_lists(g, n, hrus);
+  return group_each(g, [&](int k) {
+    const size_t nk = L.pos[k].size();
+    if (nk == 0) return (int)VICGPU_OK;
+    std::vector<T> v((size_t)nrow * nk);
+    if (op != ROWS_GET)
+      for (int r = 0; r < nrow; r++)
+        for (size_t j = 0; j < nk; j++) v[(size_t)r * nk + j] = values[(size_t)r * n + L.pos[k][j]];
+    const int* idx = hrus ? L.local[k].data() : nullptr;
+    int rc;
+    if constexpr (std::is_same<T, int>::value)
+      rc = op == ROWS_GET ? vicgpu_get_state_rows_i(g->ctx[k], nrow, rows, (int)nk, idx, v.data()) : vicgpu_update_state_i(g->ctx[k], nrow, rows, (int)nk, idx, v.data());
+    else
+      rc = op == ROWS_GET ? vicgpu_get_state_rows(g->ctx[k], nrow, rows, (int)nk, idx, v.data())
+                          : vicgpu_update_state(g->ctx[k], nrow, rows, (int)nk, idx, v.data(), op == ROWS_ADD ? VICGPU_STATE_ADD : VICGPU_STATE_SET);
+    if (rc == VICGPU_OK && op == ROWS_GET)       // the shards' positions in the caller's list are disjoint
+      for (int r = 0; r < nrow; r++)
+        for (size_t j = 0; j < nk; j++) values[(size_t)r * n + L.pos[k][j]] = v[(size_t)r * nk + j];
+    return rc;
+  });
+}
+
+extern "C" {
+
+int vicgpu_group_get_state_rows(vicgpu_group* g, int nrow, const int* rows, int n, const int* hrus, double* values) {
+  return group_state_rows<double>(g, "get_state_rows", false, ROWS_GET, nrow, rows, n, hrus, values);
+}
+
+int vicgpu_group_get_state_rows_i(vicgpu_group* g, int nrow, const int* rows, int n, const int* hrus, int* values) {
+  return group_state_rows<int>(g, "get_state_rows_i", true, ROWS_GET, nrow, rows, n, hrus, values);
+}
+
+int vicgpu_group_update_state(vicgpu_group* g, int nrow, const int* rows, int n, const int* hrus, const double* values, int mode) {
+  if (mode != VICGPU_STATE_SET && mode != VICGPU_STATE_ADD) return VICGPU_ERR_ARG;
+  return group_state_rows<double>(g, "update_state", false, mode == VICGPU_STATE_ADD ? ROWS_ADD : ROWS_SET, nrow, rows, n, hrus, const_cast<double*>(values));
+}
+
+int vicgpu_group_update_state_i(vicgpu_group* g, int nrow, const int* rows, int n, const int* hrus, const int* values) {
+  return group_state_rows<int>(g, "update_state_i", true, ROWS_SET, nrow, rows, n, hrus, const_cast<int*>(values));
+}
+
+int vicgpu_group_derive_soil_state(vicgpu_group* g, int n, const int* hrus, int what) {
+  if (!g || n < 0) return VICGPU_ERR_ARG;
+  const int rule = check_derive_what(what, g->opt.GLACIER_DYNAMICS);
+  if (rule == DERIVE_WHAT) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  if (rule == DERIVE_UNSUPPORTED) return group_fail(g, VICGPU_ERR_UNSUPPORTED, "derive_soil_state: VICGPU_DERIVE_CAP_MOIST with GLACIER_DYNAMICS");
+  if (n == 0) return VICGPU_OK;
+  const ParamFault f = check_param_update(0, g->nhru, 0, nullptr, n, hrus);
+  if (f.rule != PARAM_OK)
+    return group_fail(g, VICGPU_ERR_ARG, std::string("derive_soil_state: ") + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
+  const GroupHruLists L = group_hru_lists(g, n, hrus);
+  return group_each(g, [&](int k) {
+    const size_t nk = L.pos[k].size();
+    if (nk == 0) return (int)VICGPU_OK;
+    return vicgpu_derive_soil_state(g->ctx[k], (int)nk, hrus ? L.local[k].data() : nullptr, what);
   });
 }
 

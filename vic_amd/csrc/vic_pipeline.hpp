@@ -27,6 +27,7 @@
 #include "vic_records.hpp"
 #include "vic_copy_cells.hpp"
 #include "vic_params.hpp"
+#include "vic_state_update.hpp"
 
 using namespace vic;
 

@@ -12,6 +12,8 @@
 //   vic_copy_cells.hpp   vicgpu_copy_cells: the host planning of a copy between cells, vic_copy_direct / _pack / _unpack
 //   vic_params.hpp       vicgpu_update_cell_params / _hru_params: the host check of an update, vic_param_scatter and the
 //                        listed-cell forms of the derive kernels
+//   vic_state_update.hpp vicgpu_get_state_rows / _update_state / _derive_soil_state: vic_state_gather / _scatter on listed
+//                        state rows and vic_derive_soil_state, the tail of initialize_model_state for listed HRUs
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -44,6 +46,7 @@
 #include "vic_records.hpp"
 #include "vic_copy_cells.hpp"
 #include "vic_params.hpp"
+#include "vic_state_update.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -944,6 +947,110 @@ int vicgpu_get_hru_params(vicgpu_ctx* c, double* hru_dparams) {
   if (!c || !hru_dparams) return VICGPU_ERR_ARG;
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   return d2h(c, hru_dparams, c->dom.d_hpd);
+}
+
+// ---- model state read and changed in place, its dependent soil rows re-derived (vic_state_update.hpp): the analysis update
+// One call on listed rows of d_sd or d_si.  Everything it allocates is allocated before anything is queued: one list block
+// [rows][HRUs, when listed] and the stage.  GET: values is written; otherwise read.
+}  // extern "C": a template
+
+template <typename T>
+static int state_rows_impl(vicgpu_ctx* c, const char* name, DevBuf<T> Domain::*table, int table_rows, int op, int nrow, const int* rows, int n,
+                           const int* hrus, T* values) {
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if (nrow == 0 || n == 0) return VICGPU_OK;
+  if (!rows || !values) return VICGPU_ERR_ARG;
+  Domain& d = c->dom;
+  // every row and column is checked here, before the first write
+  const ParamFault f = check_param_update(table_rows, d.nhru, nrow, rows, n, hrus);
+  if (f.rule != PARAM_OK) {
+    c->err = std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    return VICGPU_ERR_ARG;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  DevBuf<int> lists;
+  DevBuf<T> stage;
+  HIPCHK(c, lists.alloc((size_t)nrow + (hrus ? (size_t)n : 0)));
+  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(T), nrow);
+  HIPCHK(c, stage.alloc((size_t)rpp * n));
+  std::vector<int> h(rows, rows + nrow);
+  if (hrus) h.insert(h.end(), hrus, hrus + n);
+  const int* d_rows = lists.get();
+  const int* d_hrus = hrus ? lists.get() + nrow : nullptr;
+  // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
+  // `done` event, step_impl) and precedes every step queued later
+  Event t0, t1;                    // tuning (VICGPU_STATS): the call's time on the stream, the copies of the passes included
+  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  HIPCHK(c, lists.upload(c->stream, h.data()));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  T* tab = (d.*table).get();
+  if (op == ROWS_GET) HIPCHK(c, state_gather_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp));
+  else HIPCHK(c, state_scatter_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp, op == ROWS_ADD));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
+  float ms = 0;
+  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] %s: %s, %d rows x %d HRUs, %s, %d passes, %zu bytes: %.4f ms on the stream\n", name,
+            op == ROWS_GET ? "get" : op == ROWS_SET ? "set" : "add", nrow, n, hrus ? "listed" : "dense", (nrow + rpp - 1) / rpp, sizeof(T) * nrow * n, ms);
+  return VICGPU_OK;
+}
+
+extern "C" {
+
+int vicgpu_get_state_rows(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* hrus, double* values) {
+  if (!c || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  return state_rows_impl<double>(c, "get_state_rows", &Domain::d_sd, (int)VICGPU_SD_NROW(c->o.Nnode), ROWS_GET, nrow, rows, n, hrus, values);
+}
+
+int vicgpu_get_state_rows_i(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* hrus, int* values) {
+  if (!c || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  return state_rows_impl<int>(c, "get_state_rows_i", &Domain::d_si, (int)VICGPU_SI_NROW(c->o.Nnode), ROWS_GET, nrow, rows, n, hrus, values);
+}
+
+int vicgpu_update_state(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* hrus, const double* values, int mode) {
+  if (!c || nrow < 0 || n < 0 || (mode != VICGPU_STATE_SET && mode != VICGPU_STATE_ADD)) return VICGPU_ERR_ARG;
+  return state_rows_impl<double>(c, "update_state", &Domain::d_sd, (int)VICGPU_SD_NROW(c->o.Nnode), mode == VICGPU_STATE_ADD ? ROWS_ADD : ROWS_SET, nrow,
+                                 rows, n, hrus, const_cast<double*>(values));
+}
+
+int vicgpu_update_state_i(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* hrus, const int* values) {
+  if (!c || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  return state_rows_impl<int>(c, "update_state_i", &Domain::d_si, (int)VICGPU_SI_NROW(c->o.Nnode), ROWS_SET, nrow, rows, n, hrus, const_cast<int*>(values));
+}
+
+int vicgpu_derive_soil_state(vicgpu_ctx* c, int n, const int* hrus, int what) {
+  if (!c || n < 0) return VICGPU_ERR_ARG;
+  const int rule = check_derive_what(what, c->o.GLACIER_DYNAMICS);
+  if (rule == DERIVE_WHAT) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if (rule == DERIVE_UNSUPPORTED) {
+    c->err = "derive_soil_state: VICGPU_DERIVE_CAP_MOIST with GLACIER_DYNAMICS: the excess moisture (cell.excess_moist) has no table";
+    return VICGPU_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return VICGPU_OK;
+  Domain& d = c->dom;
+  const ParamFault f = check_param_update(0, d.nhru, 0, nullptr, n, hrus);
+  if (f.rule != PARAM_OK) {
+    c->err = std::string("derive_soil_state: ") + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    return VICGPU_ERR_ARG;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  DevBuf<int> list;
+  if (hrus) HIPCHK(c, list.alloc(n));
+  Event t0, t1;                    // tuning (VICGPU_STATS): the kernel's own time
+  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  if (hrus) HIPCHK(c, list.upload(c->stream, hrus));
+  DSArgs a{};
+  a.o = c->o; a.ncell = d.ncell; a.nhru = d.nhru; a.n = n; a.what = what; a.hrus = hrus ? list.get() : nullptr;
+  a.cp = d.d_cp; a.hpi = d.d_hpi; a.hpd = d.d_hpd; a.sd = d.d_sd; a.si = d.d_si; a.flux = d.d_flux; a.cell_err = d.d_cell_err;
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, derive_soil_state(c->stream, a));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the list is released when the call returns
+  float ms = 0;
+  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] derive_soil_state: %d HRUs, %s, stages %d: %.4f ms on the device\n", n, hrus ? "listed" : "dense", what, ms);
+  return VICGPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ output records (vicgpu_out.h)
