@@ -594,6 +594,47 @@ int vicgpu_update_state(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const
 int vicgpu_update_state_i(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *hrus, const int *values);
 int vicgpu_derive_soil_state(vicgpu_ctx *ctx, int n, const int *hrus, int what);
 
+/* ---- model state combined linearly across cells on the device: the step every ensemble filter has.  An ensemble transform
+ * writes each member's analysis state as a weighted sum of the members' forecast states -- for member m at base cell j,
+ * x_a[m] = sum over m' of W_j[m'][m] * x_f[m'], W global for an ETKF or an EnKF in ensemble space and per location for a
+ * localised filter; inflation and recentring about the ensemble mean have the same form -- without pulling the rows
+ * (vicgpu_get_state_rows), multiplying on the host and pushing them (vicgpu_update_state).  vicgpu_copy_cells is the special
+ * case "one term, weight 1".
+ *   vicgpu_mix_cells   acts on the listed rows of the SD table, each in [0, VICGPU_SD_NROW(Nnode)).  Destination dst_cell[i]
+ *                      has the terms t = term_off[i] .. term_off[i + 1] - 1: cell term_cell[t] with weight term_weight[t].
+ * Pairing: as in vicgpu_copy_cells, HRUs pair by position -- the j-th HRU of the destination cell, in cell_hru_list order,
+ * combines the j-th HRUs of its term cells.  A term cell is legal for a destination under the pair rule of vicgpu_copy_cells:
+ * the same number of HRUs and, position by position, equal HPI_BAND, HPI_VEG_CLASS, HPI_IS_GLACIER, HPI_IS_ARTIFICIAL_BARE.
+ * Simultaneity: every source is read as it was before the call.  A destination may be a term of itself and of other
+ * destinations (the dense member transform is all of that); a source may repeat across destinations and within one
+ * destination; a destination must not repeat.
+ * Arithmetic (part of the contract; the library is built without floating-point contraction): for one destination HRU and
+ * one row, with the terms in list order, p = w_0 * x_0 (assigned, not added to zero), then p = p + (w_t * x_t) for t = 1, 2,
+ * ...; every product and every sum is rounded once.  The result depends on nothing else -- not the staging budget, not the cell
+ * chunks, not the kernel geometry.  A single term of weight 1.0 reproduces the source bit for bit, -0.0 included, so such a
+ * call equals vicgpu_copy_cells(VICGPU_COPY_STATE) on the listed rows.  Nothing is dropped or clamped; a zero weight still
+ * reads its operand (0 * NaN is NaN; SD_GLAC_CUM_MASS_BALANCE starts as NaN, and mixing it is the caller's decision).  No other
+ * row follows: consistency is vicgpu_derive_soil_state's, and the caller decides when.
+ * Untouched: everything vicgpu_update_state leaves untouched, the SI and FX tables, the cell flag words, and the unlisted rows
+ * and columns of SD.  The validity table is not consulted: a retired destination still takes its values.
+ * Order: as for vicgpu_copy_cells -- queued on the context's stream, behind every step queued before it (every cell chunk of
+ * the finite-difference pipeline included), ahead of every step queued after it.  The caller's buffers are free when it
+ * returns; vicgpu_synchronize and every read-back wait for it.  Records of an earlier vicgpu_run_records that are still on
+ * their way are not affected.
+ * The result always goes through a staging buffer on the device (sources are read before any destination is written), the
+ * rows in passes within VICGPU_COPY_STAGE_MB.  The term lists stay per cell on the device: their size is that of the caller's.
+ * nrow == 0 and ndst == 0 are legal and change nothing.  Every failing call leaves every table bit-identical; everything is
+ * checked, and everything is allocated, before the first write.
+ * VICGPU_ERR_ARG: a null handle; nrow < 0 or ndst < 0; null lists with work to do; a row out of range or listed twice; a
+ * destination out of range or listed twice; term_off[0] != 0 or decreasing offsets; a destination with no term; a term cell
+ * out of range; a weight that is not finite; an incompatible destination / term pair (vicgpu_last_error names the destination
+ * and the term); VICGPU_ERR_STATE: no domain; VICGPU_ERR_HIP: the runtime refused an allocation -- nothing is left behind. */
+int vicgpu_mix_cells(vicgpu_ctx *ctx, int nrow, const int *rows,
+                     int ndst, const int *dst_cell,
+                     const int *term_off,        /* [ndst+1], term_off[0] = 0, non-decreasing; nnz = term_off[ndst] */
+                     const int *term_cell,       /* [nnz], each in [0, ncell) */
+                     const double *term_weight); /* [nnz], finite */
+
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */
 int   vicgpu_set_write_fluxes(vicgpu_ctx *ctx, int on);           /* 0: skip the per-HRU flux table (accumulators still kept) */

@@ -84,6 +84,7 @@ def load_library():
         "vicgpu_update_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _dp, ctypes.c_int]),
         "vicgpu_update_state_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
         "vicgpu_derive_soil_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
+        "vicgpu_mix_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _ip, _dp]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -191,6 +192,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_forcing_map", "vicgpu_get_forcing_map", "vicgpu_copy_cells",
     "vicgpu_update_cell_params", "vicgpu_update_hru_params", "vicgpu_get_cell_params", "vicgpu_get_hru_params",
     "vicgpu_get_state_rows", "vicgpu_get_state_rows_i", "vicgpu_update_state", "vicgpu_update_state_i", "vicgpu_derive_soil_state",
+    "vicgpu_mix_cells",
 ] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
@@ -440,6 +442,21 @@ class Model:
         h = None if hrus is None else np.ascontiguousarray(hrus, dtype=np.int32)
         assert h is None or h.ndim == 1
         self._chk(self.lib.vicgpu_derive_soil_state(self.h, self.dom.nhru if h is None else len(h), None if h is None else _i(h), int(what)))
+
+    # ---- model state combined linearly across cells (the ensemble transform of a filter, inflation, recentring)
+    def mix_cells(self, rows, dst_cells, term_off, term_cell, term_weight):
+        """vicgpu_mix_cells: on the SD rows `rows`, cell dst_cells[i] becomes the sum over t in [term_off[i], term_off[i + 1]) of
+        term_weight[t] * cell term_cell[t], HRUs paired by position, in list order (w0 * x0, then + w_t * x_t, each rounded once);
+        simultaneous, so a destination may be a term of itself and of others.  domain.member_transform builds the lists of a
+        member transform.  No other row follows: derive_soil_state.  Queued behind the steps queued so far."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        d = np.ascontiguousarray(dst_cells, dtype=np.int32)
+        o = np.ascontiguousarray(term_off, dtype=np.int32)
+        c = np.ascontiguousarray(term_cell, dtype=np.int32)
+        w = np.ascontiguousarray(term_weight, dtype=np.float64)
+        assert r.ndim == 1 and d.ndim == 1 and o.shape == (len(d) + 1,) and c.ndim == 1 and w.shape == c.shape, (r.shape, d.shape, o.shape, c.shape, w.shape)
+        assert len(c) == o[-1], (len(c), int(o[-1]))
+        self._chk(self.lib.vicgpu_mix_cells(self.h, len(r), _i(r), len(d), _i(d), _i(o), _i(c), _d(w)))
 
     def get_forcing(self, step):
         f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)
@@ -714,6 +731,10 @@ class Group(Model):
 
     def records_ncol(self):
         return self.dom.ncell
+
+    # ---- a mix across shards would be an all-to-all with a summation order of its own (include/vicgpu_group.h)
+    def mix_cells(self, rows, dst_cells, term_off, term_cell, term_weight):
+        raise VicGpuError("mix_cells has no device-group form: give a shard's context (shard_ctx) the call in its local numbering")
 
     def shard_ctx(self, k):
         """Shard k's vicgpu_ctx handle, for the per-context entries (stream, tuning, debug)."""

@@ -55,6 +55,8 @@ RESOURCE_LIMITS = {
     "vic::vic_profile_solve_lockstep": (256, 0),
     "vic::vic_put_": (256, 0),
     "vic_cell_reduce": (128, 0),
+    # a small streaming kernel that lives on waves in flight: at least four per SIMD, accumulators in registers
+    "vic::vic_mix_cells": (128, 0),
 }
 
 

@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 namespace vic {
@@ -46,6 +48,40 @@ static inline void copy_pairs_from(const std::vector<int>& src_of, size_t count,
     if (src_of[d] >= 0) { out.dst.push_back((int)d); out.src.push_back(src_of[d]); }
 }
 
+// The pair rule for cells d and s (both in range): COPY_OK, or the rule the pair breaks.  cell_off / cell_list / key as below.
+static inline int copy_pair_fault(int nhru, const int* cell_off, const int* cell_list, const int* key, int nkey, int d, int s) {
+  const int nh = cell_off[d + 1] - cell_off[d];
+  if (cell_off[s + 1] - cell_off[s] != nh) return COPY_HRU_COUNT;
+  for (int j = 0; j < nh; j++) {
+    const int hd = cell_list[cell_off[d] + j], hs = cell_list[cell_off[s] + j];
+    for (int k = 0; k < nkey; k++)
+      if (key[(size_t)k * nhru + hd] != key[(size_t)k * nhru + hs]) return COPY_HRU_STRUCTURE;
+  }
+  return COPY_OK;
+}
+
+// A class per cell: two cells have the same class exactly when copy_pair_fault gives COPY_OK for them.  A call that compares
+// many pairs (vicgpu_mix_cells: every destination with every term) pays for the structure once per domain, not once per pair.
+static inline std::vector<int> copy_cell_classes(int ncell, int nhru, const int* cell_off, const int* cell_list, const int* key, int nkey) {
+  std::vector<int> cls(ncell > 0 ? ncell : 0, 0);
+  std::unordered_map<std::string, int> seen;
+  std::string sig;
+  for (int c = 0; c < ncell; c++) {
+    const int nh = cell_off[c + 1] - cell_off[c];
+    sig.resize(sizeof(int) * (size_t)nh * nkey);
+    int* w = reinterpret_cast<int*>(&sig[0]);           // nh follows from the length
+    for (int j = 0; j < nh; j++)
+      for (int k = 0; k < nkey; k++) *w++ = key[(size_t)k * nhru + cell_list[cell_off[c] + j]];
+    cls[c] = seen.emplace(sig, (int)seen.size()).first->second;
+  }
+  return cls;
+}
+
+static inline const char* copy_pair_fault_text(int fault) {
+  return fault == COPY_HRU_COUNT ? "the cells differ in their number of HRUs"
+                                 : "the cells' HRUs differ in band, vegetation class, glacier or bare-soil flag";
+}
+
 // cell_off[ncell + 1] / cell_list[nhru]: the domain's CSR; key[nkey][nhru]: the HRU rows a pair must agree in, position by
 // position.  Every pair is checked before the plan holds anything.
 static inline CopyPlan plan_cell_copy(int ncell, int nhru, const int* cell_off, const int* cell_list, const int* key, int nkey, int n,
@@ -63,14 +99,9 @@ static inline CopyPlan plan_cell_copy(int ncell, int nhru, const int* cell_off, 
   for (int i = 0; i < n; i++) {
     const int d = dst_cell[i], s = src_cell[i];
     if (d == s) { src_of[d] = -1; continue; }
-    const int nh = cell_off[d + 1] - cell_off[d];
-    if (cell_off[s + 1] - cell_off[s] != nh) return fail(COPY_HRU_COUNT, i);
-    for (int j = 0; j < nh; j++) {
-      const int hd = cell_list[cell_off[d] + j], hs = cell_list[cell_off[s] + j];
-      for (int k = 0; k < nkey; k++)
-        if (key[(size_t)k * nhru + hd] != key[(size_t)k * nhru + hs]) return fail(COPY_HRU_STRUCTURE, i);
-    }
-    ncp++; nhp += nh;
+    const int rule = copy_pair_fault(nhru, cell_off, cell_list, key, nkey, d, s);
+    if (rule != COPY_OK) return fail(rule, i);
+    ncp++; nhp += cell_off[d + 1] - cell_off[d];
   }
   copy_pairs_from(src_of, ncp, p.cell);
   std::vector<char> is_dst(ncell, 0);

@@ -28,6 +28,7 @@
 #include "vic_copy_cells.hpp"
 #include "vic_params.hpp"
 #include "vic_state_update.hpp"
+#include "vic_mix_cells.hpp"
 
 using namespace vic;
 
@@ -90,6 +91,8 @@ struct Domain {
   // host copies for vicgpu_copy_cells, which plans on the host: the CSR lists and the HRU rows a pair of cells must agree in
   // (COPY_KEY_ROWS), [COPY_NKEY][nhru]
   std::vector<int> cell_off, cell_list, copy_key;
+  std::vector<int> cell_class;     // [ncell] copy_cell_classes of them, built by the first vicgpu_mix_cells of the domain
+  MixPlan mix_plan;                // ... and the plan of its last one, whose memory the next one reuses
   // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
   bool fd = false;
   DevBuf<unsigned long long> d_ctx;
@@ -720,6 +723,8 @@ static int domain_tables(vicgpu_ctx* c, const double* cell_params, const int* hp
   d.cell_off.assign(cell_hru_offset, cell_hru_offset + ncell + 1);
   d.cell_list.assign(cell_hru_list, cell_hru_list + nhru);
   d.copy_key.resize(COPY_NKEY * nhru);
+  d.cell_class.clear();
+  d.mix_plan = MixPlan();
   for (int k = 0; k < COPY_NKEY; k++) std::copy(hpi + COPY_KEY_ROWS[k] * nhru, hpi + (COPY_KEY_ROWS[k] + 1) * nhru, d.copy_key.begin() + k * nhru);
   HIPCHK(c, d.d_sd.alloc_fill(VICGPU_SD_NROW(Nn) * nhru, 0, st));
   HIPCHK(c, d.d_si.alloc_fill(VICGPU_SI_NROW(Nn) * nhru, 0, st));
@@ -826,8 +831,7 @@ static hipError_t copy_table(vicgpu_ctx* c, int t, int what, F&& f) {
 static std::string copy_fault_text(const CopyPlan& p) {
   const char* rule = p.fault == COPY_CELL_RANGE ? "a cell is outside the domain"
                      : p.fault == COPY_DST_REPEATS ? "the destination repeats"
-                     : p.fault == COPY_HRU_COUNT ? "the cells differ in their number of HRUs"
-                                                 : "the cells' HRUs differ in band, vegetation class, glacier or bare-soil flag";
+                                                   : copy_pair_fault_text(p.fault);
   return "copy_cells: pair " + std::to_string(p.index) + ": " + rule;
 }
 

@@ -14,6 +14,7 @@
 //                        listed-cell forms of the derive kernels
 //   vic_state_update.hpp vicgpu_get_state_rows / _update_state / _derive_soil_state: vic_state_gather / _scatter on listed
 //                        state rows and vic_derive_soil_state, the tail of initialize_model_state for listed HRUs
+//   vic_mix_cells.hpp    vicgpu_mix_cells: the host planning of a linear combination across cells and vic_mix_cells
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
@@ -47,6 +48,7 @@
 #include "vic_copy_cells.hpp"
 #include "vic_params.hpp"
 #include "vic_state_update.hpp"
+#include "vic_mix_cells.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -1050,6 +1052,58 @@ int vicgpu_derive_soil_state(vicgpu_ctx* c, int n, const int* hrus, int what) {
   float ms = 0;
   if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
     fprintf(stderr, "[vicgpu] derive_soil_state: %d HRUs, %s, stages %d: %.4f ms on the device\n", n, hrus ? "listed" : "dense", what, ms);
+  return VICGPU_OK;
+}
+
+// ---- model state combined linearly across cells (vic_mix_cells.hpp): the ensemble transform of a filter, inflation, recentring
+// Everything the call allocates is allocated before anything is queued: one list block [rows][destination HRUs][their
+// destinations][their positions][term_off][term_cell], the weights and the stage.
+int vicgpu_mix_cells(vicgpu_ctx* c, int nrow, const int* rows, int ndst, const int* dst_cell, const int* term_off, const int* term_cell,
+                     const double* term_weight) {
+  if (!c || nrow < 0 || ndst < 0) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if (nrow == 0 || ndst == 0) return VICGPU_OK;
+  if (!rows || !dst_cell || !term_off || !term_cell || !term_weight) return VICGPU_ERR_ARG;
+  Domain& d = c->dom;
+  // the structure of a domain does not change: the cells' classes under the pair rule are built once
+  if (d.cell_class.empty()) d.cell_class = copy_cell_classes(d.ncell, d.nhru, d.cell_off.data(), d.cell_list.data(), d.copy_key.data(), COPY_NKEY);
+  // every list is checked here, before the first write
+  MixPlan& p = d.mix_plan;                         // kept with the domain: the next call reuses its memory
+  plan_cell_mix(p, d.ncell, d.nhru, d.cell_off.data(), d.cell_list.data(), d.copy_key.data(), COPY_NKEY, d.cell_class.data(),
+                                  (int)VICGPU_SD_NROW(c->o.Nnode), nrow, rows, ndst, dst_cell, term_off, term_cell, term_weight);
+  if (p.fault != MIX_OK) { c->err = mix_fault_text(p); return VICGPU_ERR_ARG; }
+  const int n = (int)p.size(), nnz = term_off[ndst];
+  if (n == 0) return VICGPU_OK;                    // destinations without HRUs
+  HIPCHK(c, hipSetDevice(c->device));
+  DevBuf<int> lists;
+  DevBuf<double> weights, stage;
+  HIPCHK(c, lists.alloc((size_t)nrow + 3 * (size_t)n + (size_t)ndst + 1 + (size_t)nnz));
+  HIPCHK(c, weights.alloc((size_t)nnz));
+  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
+  HIPCHK(c, stage.alloc((size_t)rpp * n));
+  MixLists l;
+  l.rows = lists.get(); l.hru = l.rows + nrow; l.dst_index = l.hru + n; l.pos = l.dst_index + n; l.term_off = l.pos + n;
+  l.term_cell = l.term_off + ndst + 1; l.term_weight = weights.get(); l.cell_off = d.d_cell_off; l.cell_list = d.d_cell_list;
+  // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
+  // `done` event, step_impl) and precedes every step queued later: the mix is queued there
+  Event t0, t1;                    // tuning (VICGPU_STATS): the kernels' own time
+  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  const size_t un = (size_t)n, at_hru = (size_t)nrow, at_off = at_hru + 3 * un, at_cell = at_off + (size_t)ndst + 1;
+  HIPCHK(c, lists.upload(c->stream, rows, 0, (size_t)nrow));
+  HIPCHK(c, lists.upload(c->stream, p.hru.data(), at_hru, un));
+  HIPCHK(c, lists.upload(c->stream, p.dst_index.data(), at_hru + un, un));
+  HIPCHK(c, lists.upload(c->stream, p.pos.data(), at_hru + 2 * un, un));
+  HIPCHK(c, lists.upload(c->stream, term_off, at_off, (size_t)ndst + 1));
+  HIPCHK(c, lists.upload(c->stream, term_cell, at_cell, (size_t)nnz));
+  HIPCHK(c, weights.upload(c->stream, term_weight));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, mix_cells_staged(c->stream, d.d_sd, (size_t)d.nhru, l, nrow, n, stage, rpp));
+  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
+  float ms = 0;
+  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+    fprintf(stderr, "[vicgpu] mix_cells: %d destinations, %d HRUs, %d terms, %d rows, %d passes, %zu bytes written: %.4f ms on the device\n", ndst, n,
+            nnz, nrow, (nrow + rpp - 1) / rpp, sizeof(double) * nrow * n, ms);
   return VICGPU_OK;
 }
 

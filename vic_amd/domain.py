@@ -489,6 +489,29 @@ def tile_members(d, nmember):
     return D, np.ascontiguousarray(np.tile(np.arange(nc, dtype=np.int32), M))
 
 
+def member_transform(nmember, ncol, W, cols=None):
+    """The lists of Model.mix_cells for an ensemble transform of the member-major ensemble of tile_members:
+    (dst_cells, term_off, term_cell, term_weight).  Member m at base column j -- cell m * ncol + j -- becomes the sum over
+    m' = 0 .. nmember - 1, ascending, of W[m', m] * cell m' * ncol + j; W is [nmember][nmember], or [ncol][nmember][nmember]
+    with one transform per base column (W[j, m', m]).  `cols` restricts the base columns (default: all, in order); the
+    destinations are listed member by member, the columns in the order given."""
+    M, nc = int(nmember), int(ncol)
+    W = np.asarray(W, dtype=np.float64)
+    assert W.shape in ((M, M), (nc, M, M)), W.shape
+    j = np.arange(nc, dtype=np.int64) if cols is None else np.asarray(cols, dtype=np.int64).reshape(-1)
+    assert j.size == 0 or (j.min() >= 0 and j.max() < nc), "a base column outside [0, ncol)"
+    m = np.arange(M, dtype=np.int64)
+    dst = (m[:, None] * nc + j[None, :]).reshape(-1)                                   # [m][j]
+    term_cell = np.broadcast_to(m[None, None, :] * nc + j[None, :, None], (M, j.size, M)).reshape(-1)      # [m][j][m']
+    if W.ndim == 2:
+        w = np.broadcast_to(W.T[:, None, :], (M, j.size, M))                           # [m][j][m'] = W[m', m]
+    else:
+        w = W[j].transpose(2, 0, 1)                                                    # [m][j][m'] = W[j, m', m]
+    term_off = np.arange(dst.size + 1, dtype=np.int64) * M
+    return (np.ascontiguousarray(dst, dtype=np.int32), np.ascontiguousarray(term_off, dtype=np.int32),
+            np.ascontiguousarray(term_cell, dtype=np.int32), np.ascontiguousarray(w, dtype=np.float64).reshape(-1))
+
+
 def make_snowflag(d, forcing, cell_col=None):
     """The per-cell snowflag uint8[nsteps][NF+1][ncell] of a derived forcing table (initialize_atmos.c:1275-1303): cell c from its
     own parameters and the air temperature and precipitation of its column cell_col[c] (None: its own column)."""
