@@ -371,6 +371,7 @@ int vicgpu_push_forcing(vicgpu_ctx *ctx, int nsteps,
  *                                density from pressure (:980-1000, plapse != 0: the PLAPSE form), vpd = svp(T) - vp clipped
  *                                at 0 (:1175-1193), the snow_step aggregation with the step mean / sum in sub-index NR, and
  *                                the snowflag (:1275-1303)
+ *   vicgpu_prefetch_forcing_perturbed  the same from shared raw columns, expanded and perturbed per forcing column (below)
  *   vicgpu_swap_forcing          makes the prefetched chunk the current one (steps already queued keep the old one)
  * so a driver overlaps the transfer of chunk k+1 with the steps of chunk k:
  *     push(0);  for k: { prefetch(k+1); step(0, n_k); swap(); }
@@ -381,6 +382,49 @@ int vicgpu_prefetch_forcing(vicgpu_ctx *ctx, int nsteps, const double *forcing, 
 int vicgpu_prefetch_forcing_raw(vicgpu_ctx *ctx, int nsteps,
                                 const double *raw,      /* [nsteps][VIC_NRAW][dt][ncell] */
                                 const int *dmy, double min_wind_speed, int plapse);
+/* ---- perturbed and expanded raw forcing: the front of a data-assimilation cycle.  An ensemble filter gets its spread from
+ * perturbed meteorology -- multiplicative noise on precipitation and shortwave, additive noise on air temperature and longwave,
+ * different for every member at every step.  The derived rows cannot be perturbed after the fact (air temperature changes vpd,
+ * the density and the snowflag), so the perturbation enters in front of the derivation: the caller uploads the shared raw
+ * columns once, nsrc wide, and the few factors; the device expands, perturbs and derives every forcing column.
+ *   ncol       the width of the context's forcing tables: ncell without a forcing map, the map's ncol with one.  The lists here
+ *              go from forcing columns to source columns and groups; the context's map still goes from cells to forcing
+ *              columns, so the two compose.
+ *   col_src    forcing column i reads source column col_src[i] of raw.  NULL: nsrc == ncol, column i reads source i.
+ *   col_group  forcing column i takes the factors of group col_group[i].  NULL: a group per column (ngroup == ncol, spatial
+ *              noise), or no perturbation (ngroup == 0).
+ *   pert       rows VICGPU_PERT_MUL(v) and VICGPU_PERT_ADD(v) of one (step, group) for raw variable v (VIC_RAW_*).
+ * The member ensemble: the identity forcing map, col_src = tile(arange(nsrc), M), col_group = repeat(arange(M), nsrc).  A
+ * calibration ensemble whose members share columns keeps its map.
+ * What a column reads: for forcing column i, step s, raw variable v and hour h the derivation reads x' = (x * mul) + add with
+ *   x = raw[s][v][h][col_src[i]], mul = pert[s][VICGPU_PERT_MUL(v)][col_group[i]], add = pert[s][VICGPU_PERT_ADD(v)][col_group[i]];
+ * the product and the sum are each rounded once (the library is built without contraction; this is part of the contract).
+ * With pert == NULL x' = x verbatim: no multiply by one, no add of zero.  Everything after that is
+ * vicgpu_prefetch_forcing_raw's derivation, unchanged and in the same order: kPa -> Pa, the MIN_WIND_SPEED floor (on the
+ * perturbed wind), the snow_step aggregation, density, vpd = svp(T) - vp with its clip, the NR slot, and the flag per cell, from
+ * that cell's parameters and its column's derived T and prec.  So the chunk it stages is bit for bit the chunk
+ * vicgpu_prefetch_forcing_raw stages from the ncol-wide table of the x'; with col_src == NULL and ngroup == 0 the call is
+ * vicgpu_prefetch_forcing_raw.  Nothing is clamped: a multiplier that makes precipitation negative is the caller's, and vapour
+ * pressure does not follow a temperature perturbation unless the caller perturbs it.
+ * Order and buffers are those of vicgpu_prefetch_forcing_raw: the copy stream, the spare slot, vicgpu_swap_forcing after it; a
+ * pinned raw is read until vicgpu_swap_forcing returns, other memory goes through the slot's staging area.  col_src, col_group
+ * and pert are free when the call returns.  The slot owns its device copies of the three lists and of the nsrc-wide raw table;
+ * they are re-used by the next call and released with the slot.
+ * Everything is checked before the first upload; a failing call leaves the current and the staged chunk as they were.
+ * VICGPU_ERR_ARG: a null handle, raw or dmy; nsteps <= 0 or nsrc < 1; a month outside 1..12; col_src == NULL with nsrc != ncol;
+ * an entry of col_src outside [0, nsrc); ngroup < 0; ngroup > 0 with pert == NULL, or pert with ngroup == 0; col_group == NULL
+ * with ngroup other than 0 or ncol; an entry of col_group outside [0, ngroup); a pert value that is not finite
+ * (vicgpu_last_error names step, row and group).  VICGPU_ERR_STATE: no domain.  VICGPU_ERR_HIP: the runtime refused an
+ * allocation -- nothing is left behind, and the slot stays usable. */
+#define VICGPU_PERT_MUL(v) (2 * (v))
+#define VICGPU_PERT_ADD(v) (2 * (v) + 1)
+#define VICGPU_NPERT       (2 * VIC_NRAW)
+int vicgpu_prefetch_forcing_perturbed(vicgpu_ctx *ctx, int nsteps,
+        int nsrc, const double *raw,        /* [nsteps][VIC_NRAW][dt][nsrc] */
+        const int *col_src,                 /* [ncol], each in [0, nsrc); NULL: nsrc must be ncol, column i reads source i */
+        int ngroup, const int *col_group,   /* [ncol], each in [0, ngroup); NULL: ngroup must be ncol (column i is group i) or 0 */
+        const double *pert,                 /* [nsteps][VICGPU_NPERT][ngroup]; NULL with ngroup == 0: no perturbation */
+        const int *dmy, double min_wind_speed, int plapse);
 int vicgpu_swap_forcing(vicgpu_ctx *ctx);
 int vicgpu_get_forcing(vicgpu_ctx *ctx, int step, double *forcing /* [VIC_NFORCE][NF+1][ncell] */,
                        unsigned char *snowflag /* [NF+1][ncell] */);       /* read-back of the current chunk (tests) */

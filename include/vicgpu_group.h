@@ -66,6 +66,13 @@ int vicgpu_group_prefetch_forcing(vicgpu_group *g, int nsteps, const double *for
                                   const int *dmy);
 int vicgpu_group_prefetch_forcing_raw(vicgpu_group *g, int nsteps, const double *raw, const int *dmy, double min_wind_speed,
                                       int plapse);
+/* vicgpu_prefetch_forcing_perturbed (vicgpu.h) with col_src[ncol] and col_group[ncol] in the caller's global column order; the
+ * whole call is checked on the whole domain before any shard uploads.  Shard k takes the forcing-column range it already holds
+ * (from column lo_k on) and uploads the range of source columns those columns name, as the same pitched copy with leading
+ * dimension nsrc; its col_src is rebased by that range's start.  Group numbers are not rebased: pert goes to every shard whole. */
+int vicgpu_group_prefetch_forcing_perturbed(vicgpu_group *g, int nsteps, int nsrc, const double *raw, const int *col_src,
+                                            int ngroup, const int *col_group, const double *pert, const int *dmy,
+                                            double min_wind_speed, int plapse);
 int vicgpu_group_swap_forcing(vicgpu_group *g);
 /* forcing map (vicgpu.h): cell_col[ncell] in the caller's global cell order, the forcing and raw tables of the entries above
  * then ncol wide, the flags ncell wide.  Shard k takes the column range [lo_k, hi_k] its cells span, with its own map rebased

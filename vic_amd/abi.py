@@ -43,12 +43,23 @@ C = _parse_header(HEADER)
 C.update(_parse_header(os.path.join(os.path.dirname(HEADER), "vicgpu_out.h")))
 # the one macro of the header that is an expression
 C["VICGPU_CELLERR_REFERENCE"] = C["VICGPU_CELLERR_SOLVER"] | C["VICGPU_CELLERR_AERO"] | C["VICGPU_CELLERR_NODES"]
+# rows of one (step, group) of the factors of vicgpu_prefetch_forcing_perturbed (VICGPU_PERT_MUL / VICGPU_PERT_ADD / VICGPU_NPERT)
+C["VICGPU_NPERT"] = 2 * C["VIC_NRAW"]
 globals().update(C)
 
 VIC_NLAYER = C["VIC_NLAYER"]
 VIC_MAX_NODES = C["VIC_MAX_NODES"]
 VIC_MAX_ZWTVMOIST = C["VIC_MAX_ZWTVMOIST"]
 VIC_NZWT_ROWS = (VIC_NLAYER + 2) * VIC_MAX_ZWTVMOIST
+
+
+def pert_mul(v):
+    """Row of raw variable v's multiplier in one (step, group) of pert (VICGPU_PERT_MUL)."""
+    return 2 * v
+
+
+def pert_add(v):
+    return 2 * v + 1
 
 
 def cp_layer(f, l):

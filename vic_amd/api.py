@@ -70,6 +70,8 @@ def load_library():
         "vicgpu_glacier_mass_balance_fit": (ctypes.c_int, [vp, _dp, ctypes.c_int]),
         "vicgpu_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
+        "vicgpu_prefetch_forcing_perturbed": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _ip, _dp, _ip,
+                                                             ctypes.c_double, ctypes.c_int]),
         "vicgpu_swap_forcing": (ctypes.c_int, [vp]),
         "vicgpu_get_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up]),
         "vicgpu_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
@@ -125,6 +127,8 @@ def load_library():
         "vicgpu_group_push_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_group_prefetch_forcing": (ctypes.c_int, [vp, ctypes.c_int, _dp, _up, _ip]),
         "vicgpu_group_prefetch_forcing_raw": (ctypes.c_int, [vp, ctypes.c_int, _dp, _ip, ctypes.c_double, ctypes.c_int]),
+        "vicgpu_group_prefetch_forcing_perturbed": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp, _ip, ctypes.c_int, _ip, _dp, _ip,
+                                                                   ctypes.c_double, ctypes.c_int]),
         "vicgpu_group_swap_forcing": (ctypes.c_int, [vp]),
         "vicgpu_group_set_forcing_map": (ctypes.c_int, [vp, ctypes.c_int, _ip]),
         "vicgpu_group_get_forcing_map": (ctypes.c_int, [vp, _ip, _ip]),
@@ -169,7 +173,7 @@ def load_library():
 # the entries of include/vicgpu_group.h that mirror a single-context entry: vicgpu_group_<name> for vicgpu_<name>
 GROUP_ENTRIES = [
     "destroy", "last_error", "set_veglib", "set_domain", "set_state", "get_state", "set_fluxes", "get_fluxes", "push_forcing",
-    "prefetch_forcing", "prefetch_forcing_raw", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
+    "prefetch_forcing", "prefetch_forcing_raw", "prefetch_forcing_perturbed", "swap_forcing", "step", "synchronize", "put_data_config", "put_data_init",
     "get_outputs", "get_balance", "get_cell_errors", "get_state_records", "set_state_records", "glacier_mass_balance_fit",
     "records_config", "records_nrow", "run_records", "records_wait", "set_retire_on_error", "set_cell_valid", "get_cell_valid",
     "set_forcing_map", "get_forcing_map", "copy_cells", "update_cell_params", "update_hru_params", "get_cell_params", "get_hru_params",
@@ -187,7 +191,7 @@ EXPORTED_SYMBOLS = [
     "vicgpu_set_fluxes", "vicgpu_get_state_records", "vicgpu_set_state_records",
     "vicgpu_records_config", "vicgpu_records_nrow", "vicgpu_run_records", "vicgpu_records_wait",
     "vicgpu_records_set_groups", "vicgpu_records_get_groups", "vicgpu_records_ncol",
-    "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
+    "vicgpu_prefetch_forcing", "vicgpu_prefetch_forcing_raw", "vicgpu_prefetch_forcing_perturbed", "vicgpu_swap_forcing", "vicgpu_get_forcing", "vicgpu_host_alloc",
     "vicgpu_host_free", "vicgpu_set_retire_on_error", "vicgpu_set_cell_valid", "vicgpu_get_cell_valid",
     "vicgpu_set_forcing_map", "vicgpu_get_forcing_map", "vicgpu_copy_cells",
     "vicgpu_update_cell_params", "vicgpu_update_hru_params", "vicgpu_get_cell_params", "vicgpu_get_hru_params",
@@ -330,6 +334,31 @@ class Model:
         assert raw.shape == (n, C["VIC_NRAW"], self.opt.dt, self.ncol), raw.shape
         self._hold_next = (raw, dmy)
         self._chk(self.lib.vicgpu_prefetch_forcing_raw(self.h, n, _d(raw), _i(dmy), float(min_wind_speed), int(bool(plapse))))
+
+    def prefetch_forcing_perturbed(self, raw, dmy, col_src=None, col_group=None, pert=None, min_wind_speed=0.0, plapse=True):
+        """vicgpu_prefetch_forcing_perturbed: raw [nsteps][VIC_NRAW][dt][nsrc] shared source columns; forcing column i (of the
+        ncol the forcing tables are wide) reads source col_src[i] (None: nsrc == ncol, its own) as x * mul + add with the
+        factors pert [nsteps][VICGPU_NPERT][ngroup] (abi.pert_mul / abi.pert_add, domain.member_perturbations) of group
+        col_group[i] (None: a group per column when pert is given); pert None: the values verbatim.  The derivation of
+        prefetch_forcing_raw follows on the device.  The lists and pert are free on return, a pinned raw after swap_forcing."""
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        dmy = np.ascontiguousarray(dmy, dtype=np.int32)
+        n = raw.shape[0]
+        assert raw.ndim == 4 and raw.shape[:3] == (n, C["VIC_NRAW"], self.opt.dt), raw.shape
+        nsrc = raw.shape[3]
+        src = None if col_src is None else np.ascontiguousarray(col_src, dtype=np.int32)
+        grp = None if col_group is None else np.ascontiguousarray(col_group, dtype=np.int32)
+        assert src is None or src.shape == (self.ncol,), src.shape
+        assert grp is None or grp.shape == (self.ncol,), grp.shape
+        ngroup = 0
+        if pert is not None:
+            pert = np.ascontiguousarray(pert, dtype=np.float64)
+            assert pert.ndim == 3 and pert.shape[:2] == (n, C["VICGPU_NPERT"]), pert.shape
+            ngroup = pert.shape[2]
+        self._hold_next = (raw, dmy)
+        self._chk(self.lib.vicgpu_prefetch_forcing_perturbed(self.h, n, nsrc, _d(raw), None if src is None else _i(src), ngroup,
+                                                             None if grp is None else _i(grp), None if pert is None else _d(pert),
+                                                             _i(dmy), float(min_wind_speed), int(bool(plapse))))
 
     def swap_forcing(self):
         self._chk(self.lib.vicgpu_swap_forcing(self.h))

@@ -57,6 +57,8 @@ RESOURCE_LIMITS = {
     "vic_cell_reduce": (128, 0),
     # a small streaming kernel that lives on waves in flight: at least four per SIMD, accumulators in registers
     "vic::vic_mix_cells": (128, 0),
+    # one lane per (step, forcing column), the 14 factors of its group in registers: no scratch, four waves per SIMD
+    "vic_derive_forcing_pert": (128, 0),
 }
 
 

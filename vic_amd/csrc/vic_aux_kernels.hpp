@@ -379,15 +379,66 @@ struct FArgs {
   const int* cell_col;         // [ncell], read by vic_derive_forcing_flags only
 };
 
-// step s: the rows of column col (VALUES) and / or the flags of cell c, whose column is col (FLAGS)
-template <bool VALUES, bool FLAGS>
-VIC_DEV void derive_forcing_lane(const FArgs& a, int s, int col, int c) {
+// Where a lane's raw values come from: raw(v, h) is variable v (VIC_RAW_*) of hour h of the lane's step and column.
+// RawDirect: column col of the ncol-wide table (vicgpu_prefetch_forcing_raw).
+struct RawDirect {
+  const double* p;
+  size_t dt, nw;
+  VIC_DEV RawDirect(const FArgs& a, int s, int col) : p(a.raw + (size_t)s * VIC_NRAW * a.dt * a.ncol + col), dt(a.dt), nw(a.ncol) {}
+  VIC_DEV double operator()(int v, int h) const { return p[((size_t)v * dt + h) * nw]; }
+};
+
+// the flags of a mapped run read the derived table, no raw value
+struct RawNone {
+  VIC_DEV double operator()(int, int) const { return 0.0; }
+};
+
+// vicgpu_prefetch_forcing_perturbed: forcing column col reads source column col_src[col] of the nsrc-wide table in a.f.raw and,
+// with PERT, the factors of group col_group[col]: x' = (x * mul) + add, the product and the sum rounded once each (the
+// library is built without contraction).  Without PERT the value is the table's, verbatim.
+struct FPArgs {
+  FArgs f;                     // f.raw: [nsteps][VIC_NRAW][dt][nsrc]
+  int nsrc, ngroup;
+  int group_base;              // the group of column 0 when col_group is null (a group per column; a shard's columns start past 0)
+  const int* col_src;          // [ncol], or null: column i reads source i
+  const int* col_group;        // [ncol], or null: column i is group group_base + i
+  const double* pert;          // [nsteps][VICGPU_NPERT][ngroup]; unread without PERT
+};
+
+// The 2 * VIC_NRAW factors of the lane's (step, group) are loaded once, here, into registers (v is a constant at every call of
+// the derivation, so mul[v] / add[v] are plain registers); nearly every lane of a wave names the same group, so the loads of a
+// wave hit one line.  The raw reads of consecutive lanes are consecutive source columns with the member-major lists.
+template <bool PERT>
+struct RawPerturbed {
+  const double* p;
+  size_t dt, nw;
+  double mul[VIC_NRAW], add[VIC_NRAW];
+  VIC_DEV RawPerturbed(const FPArgs& a, int s, int col) : dt(a.f.dt), nw(a.nsrc) {
+    p = a.f.raw + (size_t)s * VIC_NRAW * a.f.dt * a.nsrc + (a.col_src ? a.col_src[col] : col);
+    if constexpr (PERT) {
+      const double* q = a.pert + (size_t)s * VICGPU_NPERT * a.ngroup + (a.col_group ? a.col_group[col] : a.group_base + col);
+#pragma unroll
+      for (int v = 0; v < VIC_NRAW; v++) { mul[v] = q[(size_t)VICGPU_PERT_MUL(v) * a.ngroup]; add[v] = q[(size_t)VICGPU_PERT_ADD(v) * a.ngroup]; }
+    }
+  }
+  VIC_DEV double operator()(int v, int h) const {
+    const double x = p[((size_t)v * dt + h) * nw];
+    if constexpr (!PERT) return x;
+    else {
+      const double m = x * mul[v];
+      return m + add[v];
+    }
+  }
+};
+
+// step s: the rows of column col (VALUES) and / or the flags of cell c, whose column is col (FLAGS); RAW: the raw values (unread
+// without VALUES)
+template <bool VALUES, bool FLAGS, class Raw>
+VIC_DEV void derive_forcing_lane(const FArgs& a, const Raw& RAW, int s, int col, int c) {
   const size_t nc = a.ncell, nw = a.ncol;
   const int ns = a.NR + 1, NF = a.NF;
-  const double* raw = a.raw + (size_t)s * VIC_NRAW * a.dt * nw + col;
   double* f = a.forcing + (size_t)s * VIC_NFORCE * ns * nw + col;
   unsigned char* sf = a.snowflag + (size_t)s * ns * nc + c;
-#define RAW(v, h) raw[((size_t)(v) * a.dt + (h)) * nw]
 #define F(v, j) f[((size_t)(v) * ns + (j)) * nw]
   double min_Tfactor = 0, thr = 0;
   if constexpr (FLAGS) {
@@ -436,7 +487,6 @@ VIC_DEV void derive_forcing_lane(const FArgs& a, int s, int col, int c) {
     // density[NR] is derived from pressure[NR] and air_temp[NR] like every other slot (initialize_atmos.c:984-998), not averaged
     F(VIC_F_DENSITY, a.NR) = a.plapse ? (sPr / n) / (287.0 * (KELVIN + sT / n)) : 0.003486 * (sPr / n) / (275.0 + sT / n);
   }
-#undef RAW
 #undef F
 }
 
@@ -445,19 +495,29 @@ extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing(const FArgs
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)a.nsteps * a.ncell) return;
   const int s = (int)(i / a.ncell), c = (int)(i % a.ncell);
-  derive_forcing_lane<true, true>(a, s, c, c);
+  derive_forcing_lane<true, true>(a, RawDirect(a, s, c), s, c, c);
 }
 // with a map: one lane per (step, column) for the rows, then one lane per (step, cell) for the flags
 extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing_cols(const FArgs a) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)a.nsteps * a.ncol) return;
-  derive_forcing_lane<true, false>(a, (int)(i / a.ncol), (int)(i % a.ncol), 0);
+  const int s = (int)(i / a.ncol), col = (int)(i % a.ncol);
+  derive_forcing_lane<true, false>(a, RawDirect(a, s, col), s, col, 0);
 }
 extern "C" __global__ __launch_bounds__(256) void vic_derive_forcing_flags(const FArgs a) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)a.nsteps * a.ncell) return;
   const int c = (int)(i % a.ncell);
-  derive_forcing_lane<false, true>(a, (int)(i / a.ncell), a.cell_col[c], c);
+  derive_forcing_lane<false, true>(a, RawNone(), (int)(i / a.ncell), a.cell_col[c], c);
+}
+// vicgpu_prefetch_forcing_perturbed: one lane per (step, forcing column), consecutive lanes consecutive columns; the flags in
+// the same lane when there is no forcing map (FLAGS: column = cell), by vic_derive_forcing_flags after it when there is one
+template <bool FLAGS, bool PERT>
+__global__ __launch_bounds__(256) void vic_derive_forcing_pert(const FPArgs a) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)a.f.nsteps * a.f.ncol) return;
+  const int s = (int)(i / a.f.ncol), col = (int)(i % a.f.ncol);
+  derive_forcing_lane<true, FLAGS>(a.f, RawPerturbed<PERT>(a, s, col), s, col, col);
 }
 
 // the derived row of vicgpu_set_forcing_map: every HRU's forcing column, read by the step kernels next to the HPI rows

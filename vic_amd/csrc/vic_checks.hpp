@@ -1,5 +1,6 @@
 // vic_checks.hpp — the checks of what a caller hands in that need no runtime: the lists of a domain (vicgpu_set_domain and
-// vicgpu_group_set_domain) and the header of a state record (vicgpu_set_state_records and the group's).  Written once, used
+// vicgpu_group_set_domain), the header of a state record (vicgpu_set_state_records and the group's) and the lists of
+// vicgpu_prefetch_forcing_perturbed (and the group's).  Written once, used
 // by the single context and by the group.  Host code only: include/vicgpu.h and the standard library, no HIP.
 #pragma once
 #include <cstddef>
@@ -47,4 +48,37 @@ static inline DomainFault check_domain_lists(int ncell, int nhru, const int* off
 static inline std::string check_state_record(const double* rec, size_t k, int band, int veg_class) {
   if ((int)rec[SR_BAND_INDEX] == band && (int)rec[SR_VEG_CLASS] == veg_class) return std::string();
   return "state record " + std::to_string(k) + ": band / vegetation class do not match the domain (write_model_state.c:179-188)";
+}
+
+// The lists of vicgpu_prefetch_forcing_perturbed (and the group's, on the whole domain) against the width ncol of the forcing
+// tables: the empty string when the call is legal, else the message of the refusal.  nsteps > 0, nsrc >= 1 and the non-null
+// raw and dmy are the caller's to check first.
+static inline std::string check_forcing_perturbed(int ncol, int nsteps, int nsrc, const int* col_src, int ngroup, const int* col_group,
+                                                  const double* pert, const int* dmy) {
+  const std::string name = "prefetch_forcing_perturbed: ";
+  for (int s = 0; s < nsteps; s++) {
+    const int m = dmy[(size_t)s * VIC_NDMY + VIC_DMY_MONTH];
+    if (m < 1 || m > 12) return name + "step " + std::to_string(s) + ": month " + std::to_string(m) + " is not in 1..12";
+  }
+  if (!col_src && nsrc != ncol) return name + "no col_src, but nsrc is not the " + std::to_string(ncol) + " forcing columns";
+  if (col_src)
+    for (int i = 0; i < ncol; i++)
+      if (col_src[i] < 0 || col_src[i] >= nsrc) return name + "col_src entry " + std::to_string(i) + " is not a source column";
+  if (ngroup < 0) return name + "ngroup < 0";
+  if (ngroup > 0 && !pert) return name + "groups without pert";
+  if (ngroup == 0 && pert) return name + "pert without groups";
+  if (ngroup == 0 && col_group) return name + "col_group without groups";
+  if (!col_group && ngroup != 0 && ngroup != ncol) return name + "no col_group, but ngroup is neither 0 nor the " + std::to_string(ncol) + " forcing columns";
+  if (col_group)
+    for (int i = 0; i < ncol; i++)
+      if (col_group[i] < 0 || col_group[i] >= ngroup) return name + "col_group entry " + std::to_string(i) + " is not a group";
+  if (pert)
+    for (int s = 0; s < nsteps; s++)
+      for (int r = 0; r < VICGPU_NPERT; r++)
+        for (int g = 0; g < ngroup; g++) {
+          const double v = pert[((size_t)s * VICGPU_NPERT + r) * ngroup + g];
+          if (!(v - v == 0.0))       // NaN or an infinity
+            return name + "pert is not finite at step " + std::to_string(s) + ", row " + std::to_string(r) + ", group " + std::to_string(g);
+        }
+  return std::string();
 }

@@ -17,7 +17,7 @@
 
 // static helpers of vicgpu_api.hip with a pitch (ld: cells per row of the caller's table)
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
-                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag);
+                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag, const PertLists* P = nullptr);
 static int get_outputs_impl(vicgpu_ctx* c, int nvar, const int* var_ids, float* out, int reset, int ld);
 static int glacier_fit_impl(vicgpu_ctx* c, double* eq, int reset, int ld);
 static int run_records_impl(vicgpu_ctx* c, int step0, int nrecords, float* out, int* cell_err, int ld);
@@ -394,6 +394,29 @@ int vicgpu_group_prefetch_forcing_raw(vicgpu_group* g, int nsteps, const double*
   if (!group_ready(g)) return VICGPU_ERR_STATE;
   return group_each(g, [&](int k) {
     return prefetch_impl(g->ctx[k], nsteps, nullptr, nullptr, raw + g->col_lo[k], dmy, min_wind_speed, plapse, g->ncol, g->ncell);
+  });
+}
+
+// vicgpu_prefetch_forcing_perturbed (vicgpu.h) with the lists in the caller's global column order, checked on the whole domain
+// before any shard uploads.  Shard k derives the forcing columns it holds (col_lo[k] on) and uploads the range of source
+// columns those columns name -- the same pitched copy, leading dimension nsrc -- with its col_src rebased by that range's
+// start; its slice of col_group and the whole of pert go unrebased (a group per column: group = global column).
+int vicgpu_group_prefetch_forcing_perturbed(vicgpu_group* g, int nsteps, int nsrc, const double* raw, const int* col_src, int ngroup,
+                                            const int* col_group, const double* pert, const int* dmy, double min_wind_speed, int plapse) {
+  if (!g || !raw || !dmy || nsteps <= 0 || nsrc < 1) return VICGPU_ERR_ARG;
+  if (!group_ready(g)) return VICGPU_ERR_STATE;
+  const std::string why = check_forcing_perturbed(g->ncol, nsteps, nsrc, col_src, ngroup, col_group, pert, dmy);
+  if (!why.empty()) return group_fail(g, VICGPU_ERR_ARG, why);
+  if (!col_src && ngroup == 0) return vicgpu_group_prefetch_forcing_raw(g, nsteps, raw, dmy, min_wind_speed, plapse);
+  return group_each(g, [&](int k) {
+    const int lo = g->col_lo[k], width = g->ctx[k]->dom.ncol;
+    int src_lo = lo, src_n = width;              // no col_src: the shard's own columns
+    if (col_src) {
+      src_lo = *std::min_element(col_src + lo, col_src + lo + width);
+      src_n = *std::max_element(col_src + lo, col_src + lo + width) - src_lo + 1;
+    }
+    const PertLists P{src_n, col_src ? col_src + lo : nullptr, src_lo, ngroup, col_group ? col_group + lo : nullptr, lo, pert};
+    return prefetch_impl(g->ctx[k], nsteps, nullptr, nullptr, raw + src_lo, dmy, min_wind_speed, plapse, nsrc, g->ncell, &P);
   });
 }
 

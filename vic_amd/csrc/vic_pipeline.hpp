@@ -256,14 +256,18 @@ struct vicgpu_ctx {
   std::vector<int> dmy;            // host copy [nsteps][VIC_NDMY]
   int chunk_steps = 0;
   struct ForcingSlot {
-    DevBuf<double> d_f, d_raw;
+    DevBuf<double> d_f, d_raw;     // d_raw: the raw table as uploaded, ncol wide or (vicgpu_prefetch_forcing_perturbed) nsrc wide
     DevBuf<unsigned char> d_s;
+    DevBuf<double> d_pert;         // vicgpu_prefetch_forcing_perturbed: the factors and the two lists of the slot's last such call
+    DevBuf<int> d_col_src, d_col_group;
     PinnedBuf<char> h_stage;       // pinned staging for pageable sources
     std::vector<int> dmy;
     int nsteps = 0;
     Event uploaded;                // copy stream: the chunk is in the slot
     Event released;                // context stream: every step that read the slot has been queued before it
     bool upload_pending = false, was_current = false;
+    Event derive_t0, derive_t1;    // VICGPU_STATS: around the derivation kernels of the slot's last raw prefetch
+    bool derive_timed = false;     // ... both have been recorded
   } slot[2];
   int cur = -1, staged = -1;
   Stream stream, copy_stream;      // `stream` may be borrowed (vicgpu_set_stream)
@@ -276,6 +280,19 @@ struct vicgpu_ctx {
   int ev_steps = 0;                // steps covered by the event pair of the last vicgpu_step call
   int out_step_ratio = 1;
   int retire_mask = 0;             // vicgpu_set_retire_on_error; a setting of the context, not of the domain
+};
+
+// vicgpu_prefetch_forcing_perturbed as one context takes it: `raw` points at the first source column the context uploads, nsrc
+// of them, out of a table ld columns wide (a group's shard takes the range its columns name); col_src is in the numbering of
+// that table and is rebased by src_base on its way to the device; col_group and pert are never rebased
+struct PertLists {
+  int nsrc;
+  const int* col_src;          // [ncol], or null: column i reads the i-th column uploaded
+  int src_base;
+  int ngroup;
+  const int* col_group;        // [ncol], or null: column i is group group_base + i
+  int group_base;
+  const double* pert;          // [nsteps][VICGPU_NPERT][ngroup], or null: no perturbation
 };
 
 // the validity table as the kernels take it: null while every cell is known to be valid

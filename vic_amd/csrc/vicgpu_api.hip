@@ -216,9 +216,11 @@ static hipError_t upload(vicgpu_ctx* c, vicgpu_ctx::ForcingSlot& sl, void* dst, 
 }
 
 // ld: columns per row of the source forcing / raw tables (c->dom.ncol, or the global column count when a group uploads one
-// shard's columns); ld_flag: cells per row of the source flags (c->dom.ncell, or the global cell count)
+// shard's columns); ld_flag: cells per row of the source flags (c->dom.ncell, or the global cell count).  P: the raw table is
+// P->nsrc wide and every forcing column is expanded and perturbed from it (checked by the caller, check_forcing_perturbed).
+// Whatever has to grow is allocated before anything is released or uploaded: a refused allocation leaves the slot as it was.
 static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const unsigned char* snowflag, const double* raw,
-                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag) {
+                         const int* dmy, double min_wind, int plapse, int ld, int ld_flag, const PertLists* P) {
   if (!c || nsteps <= 0 || !dmy || (!raw && (!forcing || !snowflag))) return VICGPU_ERR_ARG;
   if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
@@ -229,26 +231,45 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
   const size_t nsub = c->o.NR + 1;
   const size_t ncol = c->dom.ncol;                                                            // values per column, flags per cell
   const size_t sbytes = (size_t)nsteps * nsub * c->dom.ncell, nf = (size_t)VIC_NFORCE * nsteps * nsub * ncol;      // flags (a byte each) and forcing values
-  const size_t nraw = raw ? (size_t)nsteps * VIC_NRAW * c->o.dt * ncol : 0;
+  const size_t rawcols = P ? (size_t)P->nsrc : ncol;
+  const size_t nraw = raw ? (size_t)nsteps * VIC_NRAW * c->o.dt * rawcols : 0;
   const size_t fbytes = sizeof(double) * nf, rbytes = sizeof(double) * nraw;                   // in the staging area
+  const size_t npert = (P && P->pert) ? (size_t)nsteps * VICGPU_NPERT * P->ngroup : 0;         // the factors and the two lists
+  const size_t nlsrc = (P && P->col_src) ? ncol : 0, nlgrp = (P && P->col_group) ? ncol : 0;
   const int t = (c->cur == 0) ? 1 : 0;
   vicgpu_ctx::ForcingSlot& sl = c->slot[t];
   // the slot's previous upload may still be reading its staging area; the steps that read the slot's device buffers were
   // queued before `released` was recorded (vicgpu_swap_forcing): the copy stream waits for that, not the host
   if (sl.upload_pending) { HIPCHK(c, hipEventSynchronize(sl.uploaded)); sl.upload_pending = false; }
   if (sl.was_current) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.released, 0));
-  const bool grow = nf > sl.d_f.size() || sbytes > sl.d_s.size() || nraw > sl.d_raw.size();
-  if (grow) {                                            // re-allocation: nothing may still use the old buffers
+  const size_t raw_stage = raw ? (is_pinned(raw) ? 0 : rbytes) : 0;
+  const size_t need_stage = raw ? raw_stage + sizeof(double) * npert + sizeof(int) * (nlsrc + nlgrp)      // the lists always go through it
+                                : ((is_pinned(forcing) ? 0 : fbytes) + (is_pinned(snowflag) ? 0 : sbytes));
+  DevBuf<double> g_f, g_raw, g_pert;
+  DevBuf<unsigned char> g_s;
+  DevBuf<int> g_src, g_grp;
+  PinnedBuf<char> g_stage;
+  if (nf > sl.d_f.size()) HIPCHK(c, g_f.alloc(nf));
+  if (sbytes > sl.d_s.size()) HIPCHK(c, g_s.alloc(sbytes));
+  if (nraw > sl.d_raw.size()) HIPCHK(c, g_raw.alloc(nraw));
+  if (npert > sl.d_pert.size()) HIPCHK(c, g_pert.alloc(npert));
+  if (nlsrc > sl.d_col_src.size()) HIPCHK(c, g_src.alloc(nlsrc));
+  if (nlgrp > sl.d_col_group.size()) HIPCHK(c, g_grp.alloc(nlgrp));
+  if (need_stage > sl.h_stage.size()) HIPCHK(c, g_stage.alloc(need_stage));
+  if (g_f || g_s || g_raw || g_pert || g_src || g_grp) {      // re-allocation: nothing may still use the old buffers
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     if (sl.was_current) HIPCHK(c, hipEventSynchronize(sl.released));
-    HIPCHK(c, sl.d_f.reserve(nf));
-    HIPCHK(c, sl.d_s.reserve(sbytes));
-    HIPCHK(c, sl.d_raw.reserve(nraw));
   }
-  const size_t need_stage = raw ? (is_pinned(raw) ? 0 : rbytes) : ((is_pinned(forcing) ? 0 : fbytes) + (is_pinned(snowflag) ? 0 : sbytes));
-  HIPCHK(c, sl.h_stage.reserve(need_stage));
+  // every allocation got through: the slot takes the new buffers and the old ones go
+  if (g_f) { sl.d_f = std::move(g_f); g_f.reset(); }
+  if (g_s) { sl.d_s = std::move(g_s); g_s.reset(); }
+  if (g_raw) { sl.d_raw = std::move(g_raw); g_raw.reset(); }
+  if (g_pert) { sl.d_pert = std::move(g_pert); g_pert.reset(); }
+  if (g_src) { sl.d_col_src = std::move(g_src); g_src.reset(); }
+  if (g_grp) { sl.d_col_group = std::move(g_grp); g_grp.reset(); }
+  if (g_stage) { sl.h_stage = std::move(g_stage); g_stage.reset(); }
   if (raw) {
-    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * ncol, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
+    HIPCHK(c, upload(c, sl, sl.d_raw, raw, sizeof(double) * rawcols, (size_t)nsteps * VIC_NRAW * c->o.dt, sizeof(double) * ld, 0));
     FArgs a;
     a.nsteps = nsteps; a.ncell = c->dom.ncell; a.dt = c->o.dt; a.snow_step = c->o.snow_step; a.NF = c->o.NF; a.NR = c->o.NR;
     a.temp_th_type = c->o.TEMP_TH_TYPE; a.Nband = c->o.Nband; a.Nnode = c->o.Nnode; a.plapse = plapse;
@@ -256,15 +277,51 @@ static int prefetch_impl(vicgpu_ctx* c, int nsteps, const double* forcing, const
     a.min_wind = (double)(float)min_wind;        // options.MIN_WIND_SPEED is a float (vicNl_def.h:713)
     a.raw = sl.d_raw; a.cell_params = c->dom.d_cp; a.forcing = sl.d_f; a.snowflag = sl.d_s;
     const size_t n = (size_t)nsteps * c->dom.ncell, nc = (size_t)nsteps * ncol;
-    if (!c->dom.d_cell_col) hipLaunchKernelGGL(vic_derive_forcing, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
-    else {                                       // the rows once per column, then every cell's flag from its column's rows
-      hipLaunchKernelGGL(vic_derive_forcing_cols, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, c->copy_stream, a);
-      hipLaunchKernelGGL(vic_derive_forcing_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->copy_stream, a);
+    const dim3 gcell((unsigned)((n + 255) / 256)), gcol((unsigned)((nc + 255) / 256)), block(256);
+    FPArgs pa;
+    if (P) {                                     // the factors and the lists: staged behind the raw table, free when the call returns
+      char* st = sl.h_stage + raw_stage;
+      if (npert) {
+        memcpy(st, P->pert, sizeof(double) * npert);
+        HIPCHK(c, hipMemcpyAsync(sl.d_pert.get(), st, sizeof(double) * npert, hipMemcpyHostToDevice, c->copy_stream));
+        st += sizeof(double) * npert;
+      }
+      if (nlsrc) {
+        int* l = (int*)st;
+        for (size_t i = 0; i < ncol; i++) l[i] = P->col_src[i] - P->src_base;
+        HIPCHK(c, hipMemcpyAsync(sl.d_col_src.get(), st, sizeof(int) * ncol, hipMemcpyHostToDevice, c->copy_stream));
+        st += sizeof(int) * ncol;
+      }
+      if (nlgrp) {
+        memcpy(st, P->col_group, sizeof(int) * ncol);
+        HIPCHK(c, hipMemcpyAsync(sl.d_col_group.get(), st, sizeof(int) * ncol, hipMemcpyHostToDevice, c->copy_stream));
+      }
+      pa.f = a; pa.nsrc = P->nsrc; pa.ngroup = P->ngroup; pa.group_base = P->group_base;
+      pa.col_src = nlsrc ? sl.d_col_src.get() : nullptr; pa.col_group = nlgrp ? sl.d_col_group.get() : nullptr;
+      pa.pert = npert ? sl.d_pert.get() : nullptr;
     }
+    if (c->tune.stats && !sl.derive_t0) { HIPCHK(c, sl.derive_t0.create()); HIPCHK(c, sl.derive_t1.create()); }
+    const bool timed = c->tune.stats;
+    if (timed) HIPCHK(c, hipEventRecord(sl.derive_t0, c->copy_stream));
+    const bool mapped = c->dom.d_cell_col;
+    if (P) {                                     // rows (and, without a map, flags) per forcing column
+      if (mapped) {
+        if (npert) hipLaunchKernelGGL((vic_derive_forcing_pert<false, true>), gcol, block, 0, c->copy_stream, pa);
+        else hipLaunchKernelGGL((vic_derive_forcing_pert<false, false>), gcol, block, 0, c->copy_stream, pa);
+      } else {
+        if (npert) hipLaunchKernelGGL((vic_derive_forcing_pert<true, true>), gcol, block, 0, c->copy_stream, pa);
+        else hipLaunchKernelGGL((vic_derive_forcing_pert<true, false>), gcol, block, 0, c->copy_stream, pa);
+      }
+    } else if (!mapped) hipLaunchKernelGGL(vic_derive_forcing, gcell, block, 0, c->copy_stream, a);
+    else hipLaunchKernelGGL(vic_derive_forcing_cols, gcol, block, 0, c->copy_stream, a);      // the rows once per column
+    if (mapped) hipLaunchKernelGGL(vic_derive_forcing_flags, gcell, block, 0, c->copy_stream, a);      // every cell's flag from its column's rows
     HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(sl.derive_t1, c->copy_stream));
+    sl.derive_timed = timed;
   } else {
     HIPCHK(c, upload(c, sl, sl.d_f, forcing, sizeof(double) * ncol, (size_t)nsteps * VIC_NFORCE * nsub, sizeof(double) * ld, 0));
     HIPCHK(c, upload(c, sl, sl.d_s, snowflag, c->dom.ncell, (size_t)nsteps * nsub, ld_flag, is_pinned(forcing) ? 0 : fbytes));
+    sl.derive_timed = false;
   }
   HIPCHK(c, hipEventRecord(sl.uploaded, c->copy_stream));
   sl.upload_pending = true;
@@ -282,6 +339,16 @@ int vicgpu_prefetch_forcing_raw(vicgpu_ctx* c, int nsteps, const double* raw, co
   if (!raw) return VICGPU_ERR_ARG;
   return c ? prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->dom.ncol, c->dom.ncell) : VICGPU_ERR_ARG;
 }
+int vicgpu_prefetch_forcing_perturbed(vicgpu_ctx* c, int nsteps, int nsrc, const double* raw, const int* col_src, int ngroup,
+                                      const int* col_group, const double* pert, const int* dmy, double min_wind_speed, int plapse) {
+  if (!c || !raw || !dmy || nsteps <= 0 || nsrc < 1) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  c->err = check_forcing_perturbed(c->dom.ncol, nsteps, nsrc, col_src, ngroup, col_group, pert, dmy);
+  if (!c->err.empty()) return VICGPU_ERR_ARG;
+  if (!col_src && ngroup == 0) return prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, c->dom.ncol, c->dom.ncell);
+  const PertLists P{nsrc, col_src, 0, ngroup, col_group, 0, pert};
+  return prefetch_impl(c, nsteps, nullptr, nullptr, raw, dmy, min_wind_speed, plapse, nsrc, c->dom.ncell, &P);
+}
 
 int vicgpu_swap_forcing(vicgpu_ctx* c) {
   if (!c) return VICGPU_ERR_ARG;
@@ -295,6 +362,12 @@ int vicgpu_swap_forcing(vicgpu_ctx* c) {
   // the source buffer (pinned user memory or the staging area) is free again once the upload has finished
   HIPCHK(c, hipEventSynchronize(sl.uploaded));
   sl.upload_pending = false;
+  if (sl.derive_timed) {                                  // tuning (VICGPU_STATS): what the derivation of this chunk took on the device
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, sl.derive_t0, sl.derive_t1) == hipSuccess)
+      fprintf(stderr, "[vicgpu] forcing derive: %d steps, %d columns, %d cells: %.4f ms\n", sl.nsteps, c->dom.ncol, c->dom.ncell, ms);
+    sl.derive_timed = false;
+  }
   c->cur = c->staged; c->staged = -1;
   c->d_forcing = sl.d_f; c->d_snowflag = sl.d_s; c->dmy = sl.dmy; c->chunk_steps = sl.nsteps;
   return VICGPU_OK;

@@ -512,6 +512,52 @@ def member_transform(nmember, ncol, W, cols=None):
             np.ascontiguousarray(term_cell, dtype=np.int32), np.ascontiguousarray(w, dtype=np.float64).reshape(-1))
 
 
+PERTURBED = ("VIC_RAW_PREC", "VIC_RAW_SHORTWAVE", "VIC_RAW_AIR_TEMP", "VIC_RAW_LONGWAVE")      # the generator's draw order
+MULTIPLICATIVE = ("VIC_RAW_PREC", "VIC_RAW_SHORTWAVE")
+
+
+def member_perturbations(nmember, nsteps, step_hours, std, tau_hours, state=None, seed=SEED):
+    """(pert, state): the factors pert [nsteps][VICGPU_NPERT][nmember] of Model.prefetch_forcing_perturbed for a member ensemble
+    (col_group = repeat(arange(nmember), nsrc)), and what the next chunk continues from.
+    std: {raw variable: sigma} for precipitation and shortwave (multipliers exp(sigma * r - sigma^2 / 2), whose mean is 1)
+    and air temperature and longwave (addends sigma * r); the variable by name ("VIC_RAW_PREC") or row.  Every row not asked
+    for -- and every one with sigma 0 -- stays at multiplier exactly 1.0 and addend exactly 0.0.  r is AR(1) noise of unit
+    variance per member and variable: r_t = phi * r_(t-1) + sqrt(1 - phi^2) * eps with phi = exp(-step_hours / tau_hours)
+    (tau_hours a number or {variable: hours}; 0: white noise), started from a draw of its stationary distribution.
+    state: None starts a generator from `seed`; the state a call returns carries r and the generator, so two chunks
+    generated in sequence equal one long chunk bit for bit (every call draws all four variables, asked for or not)."""
+    M, n = int(nmember), int(nsteps)
+    name = {C[v]: v for v in PERTURBED}
+    sigma = {}
+    for k, v in dict(std).items():
+        k = name.get(k, k)
+        assert k in PERTURBED, "no perturbation is defined for %s" % (k,)
+        sigma[k] = float(v)
+    tau = {name.get(k, k): float(v) for k, v in tau_hours.items()} if isinstance(tau_hours, dict) else {v: float(tau_hours) for v in PERTURBED}
+    phi = np.array([np.exp(-float(step_hours) / tau[v]) if tau.get(v, 0.0) > 0 else 0.0 for v in PERTURBED])[:, None]
+    if state is None:
+        rng = np.random.default_rng(seed)
+        r = rng.standard_normal((len(PERTURBED), M))
+    else:
+        rng, r = state["rng"], state["r"].copy()
+        assert r.shape == (len(PERTURBED), M), r.shape
+    eps = rng.standard_normal((n, len(PERTURBED), M))
+    pert = np.zeros((n, C["VICGPU_NPERT"], M))
+    pert[:, 0::2] = 1.0
+    innov = np.sqrt(1.0 - phi * phi)
+    for t in range(n):
+        r = phi * r + innov * eps[t]
+        for i, v in enumerate(PERTURBED):
+            s = sigma.get(v, 0.0)
+            if s == 0.0:
+                continue
+            if v in MULTIPLICATIVE:
+                pert[t, abi.pert_mul(C[v])] = np.exp(s * r[i] - s * s / 2)
+            else:
+                pert[t, abi.pert_add(C[v])] = s * r[i]
+    return np.ascontiguousarray(pert), {"rng": rng, "r": r}
+
+
 def make_snowflag(d, forcing, cell_col=None):
     """The per-cell snowflag uint8[nsteps][NF+1][ncell] of a derived forcing table (initialize_atmos.c:1275-1303): cell c from its
     own parameters and the air temperature and precipitation of its column cell_col[c] (None: its own column)."""
