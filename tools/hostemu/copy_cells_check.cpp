@@ -82,7 +82,7 @@ static void run_table(const Dom& d, const CopyPlan& p, int nrow, const std::vect
     CHECK(p.direct);
     CHECK(copy_direct<T>(stream, table, d.nhru, nrow, d_dst, d_src, np) == hipSuccess);
   } else {
-    const int rpp = copy_rows_per_pass((size_t)budget, np, sizeof(T), nrow);
+    const int rpp = rows_per_pass((size_t)budget, np, sizeof(T), nrow);
     CHECK(rpp >= 1 && rpp <= nrow && (rpp == 1 || (size_t)rpp * np * sizeof(T) <= (size_t)budget));
     if (passes) *passes = (nrow + rpp - 1) / rpp;
     T* stage = nullptr;
@@ -109,7 +109,7 @@ int main() {
   const int M = 4, NB = 70;                // 4 members of 70 cells and 209 HRUs: pair lists end inside a wave
   const Dom d = make_dom(M, NB);
   CHECK(d.nhru == M * 209 && d.nhru % 64 != 0);
-  const int NROW_D = 19, NROW_I = 11;      // no multiple of CC_ROWS: the last row tile is ragged
+  const int NROW_D = 19, NROW_I = 11;      // no multiple of ROW_TILE: the last row tile is ragged
   struct Pattern { const char* name; std::vector<int> dst, src; bool direct; size_t ncell_pairs; };
   std::vector<Pattern> pats(4);
   pats[0].name = "fan-out"; pats[0].direct = true;

@@ -108,7 +108,7 @@ static int run_mix(const Dom& d, int table_rows, const Call& c, size_t budget) {
   int *d_rows = to_device(c.rows), *d_hru = to_device(p.hru), *d_index = to_device(p.dst_index), *d_pos = to_device(p.pos);
   int *d_off = to_device(c.off), *d_cell = to_device(c.cell), *d_coff = to_device(d.off), *d_clist = to_device(d.list);
   double* d_weight = to_device(c.weight);
-  const int rpp = copy_rows_per_pass(budget, (size_t)n, sizeof(double), nrow);
+  const int rpp = rows_per_pass(budget, (size_t)n, sizeof(double), nrow);
   double* stage = nullptr;
   CHECK(hipMalloc(&stage, sizeof(double) * rpp * n) == hipSuccess);                // exactly what a pass may use
   MixLists l;

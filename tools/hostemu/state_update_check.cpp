@@ -1,6 +1,6 @@
 // state_update_check.cpp — vic_amd/csrc/vic_state_update.hpp as a stand-alone program under ASan + UBSan: the check of a call,
-// the gather and scatter kernels (SET and ADD, double and int) through their staged launchers, and vic_derive_soil_state for
-// the three node bounds, on tables built here with exact-size allocations (the stand-in hip/hip_runtime.h of this directory
+// the gather and scatter kernels of vic_rows.hpp (SET and ADD, double and int) through their staged launchers, and
+// vic_derive_soil_state for the three node bounds, on tables built here with exact-size allocations (the stand-in hip/hip_runtime.h of this directory
 // mallocs "device" memory), so a stray column, row or node is a sanitizer report.  Ragged lists (no multiple of a wave), the
 // dense form, one-row passes and ragged last passes against a plain loop; the derive against what its stages must leave.
 // Built and run by tests/test_state_update.py; exit status 0 = every check held.
@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "vic_aux_kernels.hpp"     // vic_derive_cell_params: the appended rows of the parameter table the derive reads
 #include "vic_state_update.hpp"
 
 using namespace vic;
@@ -58,18 +59,18 @@ static int run_rows(int table_rows, int ld, const std::vector<int>& rows, const 
   T* table = to_device(t);
   int* d_rows = to_device(rows);
   int* d_cols = cols.empty() ? nullptr : to_device(cols);
-  const int rpp = copy_rows_per_pass(budget, (size_t)n, sizeof(T), nrow);
+  const int rpp = rows_per_pass(budget, (size_t)n, sizeof(T), nrow);
   CHECK(rpp >= 1 && rpp <= nrow && (rpp == 1 || (size_t)rpp * n * sizeof(T) <= budget));
   T* stage = nullptr;
   CHECK(hipMalloc(&stage, sizeof(T) * rpp * n) == hipSuccess);                   // exactly what a pass may use
   std::vector<T> got(v.size());                                                  // exactly what a get may write
-  CHECK(state_gather_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, got.data(), stage, rpp) == hipSuccess);
+  CHECK(rows_get_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, got.data(), stage, rpp) == hipSuccess);
   CHECK(memcmp(got.data(), slice.data(), sizeof(T) * got.size()) == 0);
-  CHECK(state_scatter_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, v.data(), stage, rpp, add) == hipSuccess);
+  CHECK(rows_put_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, v.data(), stage, rpp, add) == hipSuccess);
   const std::vector<T> after = to_host(table, t.size());
   CHECK(memcmp(after.data(), want.data(), sizeof(T) * after.size()) == 0);
   CHECK(memcmp(after.data(), t.data(), sizeof(T) * after.size()) != 0);
-  CHECK(state_gather_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, got.data(), stage, rpp) == hipSuccess);
+  CHECK(rows_get_staged<T>(stream, table, ld, d_rows, nrow, d_cols, n, got.data(), stage, rpp) == hipSuccess);
   for (int k = 0; k < nrow; k++)
     for (int i = 0; i < n; i++) CHECK(memcmp(&got[(size_t)k * n + i], &want[at(k, i)], sizeof(T)) == 0);
   CHECK(hipFree(stage) == hipSuccess && hipFree(table) == hipSuccess && hipFree(d_rows) == hipSuccess);
@@ -197,7 +198,7 @@ static void run_derive(int Nn, int quick_flux) {
 }
 
 int main() {
-  // ---- gather and scatter: 19 rows of a 23-row table (no multiple of PU_ROWS, out of order), 209 of 280 columns (ends inside a wave)
+  // ---- gather and scatter: 19 rows of a 23-row table (no multiple of ROW_TILE, out of order), 209 of 280 columns (ends inside a wave)
   const int TR = 23, LD = 280;
   std::vector<int> rows, cols;
   for (int k = 0; k < 19; k++) rows.push_back((k * 7 + 3) % TR);

@@ -1,6 +1,6 @@
-// update_params_check.cpp — vic_amd/csrc/vic_params.hpp as a stand-alone program under ASan + UBSan: the check of a call, the
-// owner cells of listed HRUs, the scatter kernel through its staged launcher and the listed-cell derive kernels, on tables
-// built here with exact-size allocations (the stand-in hip/hip_runtime.h of this directory mallocs "device" memory), so a
+// update_params_check.cpp — vic_amd/csrc/vic_params.hpp as a stand-alone program under ASan + UBSan: the check of a call and
+// the scatter kernel through its staged launcher (both of vic_rows.hpp), the owner cells of listed HRUs and the listed-cell
+// derive kernels, on tables built here with exact-size allocations (the stand-in hip/hip_runtime.h mallocs "device" memory), so a
 // stray column or row is a sanitizer report.  Ragged lists (no multiple of a wave), the dense form, one-row passes and ragged
 // last passes against a plain loop, plus what the check must refuse.  Built and run by tests/test_update_params.py; exit
 // status 0 = every check held.
@@ -45,11 +45,11 @@ static int run_scatter(int table_rows, int ld, const std::vector<int>& rows, con
   double* table = to_device(t);
   int* d_rows = to_device(rows);
   int* d_cols = cols.empty() ? nullptr : to_device(cols);
-  const int rpp = copy_rows_per_pass(budget, (size_t)n, sizeof(double), nrow);
+  const int rpp = rows_per_pass(budget, (size_t)n, sizeof(double), nrow);
   CHECK(rpp >= 1 && rpp <= nrow && (rpp == 1 || (size_t)rpp * n * sizeof(double) <= budget));
   double* stage = nullptr;
   CHECK(hipMalloc(&stage, sizeof(double) * rpp * n) == hipSuccess);              // exactly what a pass may use
-  CHECK(param_scatter_staged(stream, table, ld, d_rows, nrow, d_cols, n, v.data(), stage, rpp) == hipSuccess);
+  CHECK(rows_put_staged<double>(stream, table, ld, d_rows, nrow, d_cols, n, v.data(), stage, rpp) == hipSuccess);
   std::vector<double> got(t.size());
   CHECK(hipMemcpy(got.data(), table, sizeof(double) * got.size(), hipMemcpyDeviceToHost) == hipSuccess);
   CHECK(memcmp(got.data(), want.data(), sizeof(double) * got.size()) == 0);
@@ -64,7 +64,7 @@ static ParamFault chk(int table_rows, int ncol, const std::vector<int>& rows, co
 }
 
 int main() {
-  // ---- the scatter: 19 rows of a 23-row table (no multiple of PU_ROWS, out of order), 209 of 280 columns (ends inside a wave)
+  // ---- the scatter: 19 rows of a 23-row table (no multiple of ROW_TILE, out of order), 209 of 280 columns (ends inside a wave)
   const int TR = 23, LD = 280;
   std::vector<int> rows, cols;
   for (int k = 0; k < 19; k++) rows.push_back((k * 7 + 3) % TR);

@@ -57,6 +57,9 @@ RESOURCE_LIMITS = {
     "vic_cell_reduce": (128, 0),
     # a small streaming kernel that lives on waves in flight: at least four per SIMD, accumulators in registers
     "vic::vic_mix_cells": (128, 0),
+    # the row gather and scatter (vic_rows.hpp): eight values in flight per lane and nothing else, full occupancy, no scratch;
+    # a ceiling a little above today's 22 VGPRs
+    "vic::vic_rows_": (32, 0),
     # one lane per (step, forcing column), the 14 factors of its group in registers: no scratch, four waves per SIMD
     "vic_derive_forcing_pert": (128, 0),
 }

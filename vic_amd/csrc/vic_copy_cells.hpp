@@ -1,6 +1,6 @@
 // vic_copy_cells.hpp — model state copied between cells on the device (vicgpu_copy_cells, include/vicgpu.h): the planning of
-// a call on the host, the column-gather kernels for gfx950 and their launchers.  Nothing here knows a context: the tables are
-// [nrow][ld] arrays of double or int, the pairs are column indices.
+// a call on the host, the direct kernel for gfx950 and the launchers of both paths.  Nothing here knows a context: the tables
+// are [nrow][ld] arrays of double or int, the pairs are column indices.
 //
 //   plan_cell_copy     (host, no HIP) checks a call's cell pairs -- range, repeated destination, equal HRU structure position
 //                      by position -- before anything is written, drops the identity pairs and turns the rest into cell
@@ -9,20 +9,21 @@
 //                      consecutive columns where destination cells are contiguous (member-major ensembles).  It also says
 //                      whether the direct path is legal: no destination is the source of another remaining pair.
 //   vic_copy_direct    T[r][dst_j] = T[r][src_j]: one kernel per table.  Legal on the direct path only -- a lane then reads
-//                      columns no lane writes.
-//   vic_copy_pack      stage[r][j] = T[r][src_j]
-//   vic_copy_unpack    T[r][dst_j] = stage[r][j]: the staged path, for permutations (every source is read as it was before
-//                      the call).  The rows go in passes of at most `rows_per_pass` rows, so the stage never exceeds a budget
-//                      (copy_rows_per_pass); the passes are independent, because a row is read and written within its own pass.
-// Geometry of vic_out_group_reduce: a lane is one pair and a tile of CC_ROWS rows (blockIdx.y); the two indices are loaded once
-// and reused for the tile's rows; a tile's loads are all issued before its stores.  One template over the element type.  No
-// LDS, no scratch, plain vector loads and stores.  The kernels trust their indices: plan_cell_copy has checked them.
+//                      columns no lane writes.  Geometry of vic_rows.hpp: a lane is one pair and a tile of ROW_TILE rows
+//                      (blockIdx.y); the two indices are loaded once and reused for the tile's rows; a tile's loads are all
+//                      issued before its stores.  No LDS, no scratch, plain vector loads and stores.
+//   copy_pack          stage[r][j] = T[r][src_j]: vic_rows_gather on consecutive rows
+//   copy_unpack        T[r][dst_j] = stage[r][j]: vic_rows_scatter on them.  The staged path, for permutations (every source is
+//                      read as it was before the call).  The rows go in passes of at most `rows_per_pass` rows, so the stage
+//                      never exceeds a budget; the passes are independent, because a row is read and written within its own pass.
+// The kernels trust their indices: plan_cell_copy has checked them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <string>
 #include <unordered_map>
 #include <vector>
+#include "vic_rows.hpp"
 
 namespace vic {
 
@@ -116,117 +117,62 @@ static inline CopyPlan plan_cell_copy(int ncell, int nhru, const int* cell_off, 
   return p;
 }
 
-// Rows a pass of the staged path may hold: as many as fit into budget_bytes, at least one, at most all
-static inline int copy_rows_per_pass(size_t budget_bytes, size_t npair, size_t elem_bytes, int nrow) {
-  const size_t row = npair * elem_bytes;
-  const size_t fit = row ? budget_bytes / row : (size_t)nrow;
-  return fit < 1 ? 1 : (fit > (size_t)nrow ? nrow : (int)fit);
-}
-
 // ------------------------------------------------------------------------------------------------ kernels
-constexpr int CC_ROWS = 8;         // rows per launch row (blockIdx.y): values a lane holds between its loads and its stores
-
 template <typename T>
 struct CCArgs {
-  int npair, nrow;                 // pairs; rows of this launch, counted from the row `table` and `stage` point to
+  int npair, nrow;                 // pairs; rows of the table
   size_t ld;                       // columns per row of the table
-  const int* dst;                  // [npair] (direct, unpack)
-  const int* src;                  // [npair] (direct, pack)
+  const int* dst;                  // [npair]
+  const int* src;                  // [npair]
   T* table;                        // [nrow][ld]
-  T* stage;                        // [nrow][npair] (pack, unpack)
 };
 
 template <typename T>
 __global__ __launch_bounds__(64) void vic_copy_direct(const CCArgs<T> a) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= a.npair) return;
-  const int r0 = blockIdx.y * CC_ROWS;
+  const int r0 = blockIdx.y * ROW_TILE;
   const T* in = a.table + (size_t)r0 * a.ld + a.src[j];
   T* out = a.table + (size_t)r0 * a.ld + a.dst[j];
-  T v[CC_ROWS];
+  T v[ROW_TILE];
 #pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
+  for (int i = 0; i < ROW_TILE; i++)
     if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.ld];
 #pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
-    if (r0 + i < a.nrow) out[(size_t)i * a.ld] = v[i];
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void vic_copy_pack(const CCArgs<T> a) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= a.npair) return;
-  const int r0 = blockIdx.y * CC_ROWS;
-  const T* __restrict__ in = a.table + (size_t)r0 * a.ld + a.src[j];
-  T* __restrict__ out = a.stage + (size_t)r0 * a.npair + j;
-  T v[CC_ROWS];
-#pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
-    if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.ld];
-#pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
-    if (r0 + i < a.nrow) out[(size_t)i * a.npair] = v[i];
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void vic_copy_unpack(const CCArgs<T> a) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= a.npair) return;
-  const int r0 = blockIdx.y * CC_ROWS;
-  const T* __restrict__ in = a.stage + (size_t)r0 * a.npair + j;
-  T* __restrict__ out = a.table + (size_t)r0 * a.ld + a.dst[j];
-  T v[CC_ROWS];
-#pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
-    if (r0 + i < a.nrow) v[i] = in[(size_t)i * a.npair];
-#pragma unroll
-  for (int i = 0; i < CC_ROWS; i++)
+  for (int i = 0; i < ROW_TILE; i++)
     if (r0 + i < a.nrow) out[(size_t)i * a.ld] = v[i];
 }
 
 // ------------------------------------------------------------------------------------------------ launchers (host)
-static inline dim3 copy_grid(int npair, int nrow) { return dim3((unsigned)((npair + 63) / 64), (unsigned)((nrow + CC_ROWS - 1) / CC_ROWS)); }
-
 // every row of table[nrow][ld] on the direct path; d_dst / d_src: the pairs in device memory
 template <typename T>
 static inline hipError_t copy_direct(hipStream_t st, T* table, size_t ld, int nrow, const int* d_dst, const int* d_src, int npair) {
   if (npair <= 0 || nrow <= 0) return hipSuccess;
-  CCArgs<T> a;
-  a.npair = npair; a.nrow = nrow; a.ld = ld; a.dst = d_dst; a.src = d_src; a.table = table; a.stage = nullptr;
-  hipLaunchKernelGGL((vic_copy_direct<T>), copy_grid(npair, nrow), dim3(64), 0, st, a);
+  const CCArgs<T> a{npair, nrow, ld, d_dst, d_src, table};
+  hipLaunchKernelGGL((vic_copy_direct<T>), rows_grid(npair, nrow), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 
 // rows [r0, r0 + nr) of table[..][ld]: the columns d_src[0 .. npair) into stage[nr][npair]
 template <typename T>
 static inline hipError_t copy_pack(hipStream_t st, const T* table, size_t ld, int r0, int nr, const int* d_src, int npair, T* stage) {
-  if (npair <= 0 || nr <= 0) return hipSuccess;
-  CCArgs<T> a;
-  a.npair = npair; a.nrow = nr; a.ld = ld; a.dst = nullptr; a.src = d_src; a.table = const_cast<T*>(table) + (size_t)r0 * ld; a.stage = stage;
-  hipLaunchKernelGGL((vic_copy_pack<T>), copy_grid(npair, nr), dim3(64), 0, st, a);
-  return hipGetLastError();
+  return rows_gather<T>(st, table + (size_t)r0 * ld, ld, nullptr, nr, d_src, npair, stage);
 }
 
 // ... and stage[nr][npair] into the columns d_dst[0 .. npair) of those rows
 template <typename T>
 static inline hipError_t copy_unpack(hipStream_t st, T* table, size_t ld, int r0, int nr, const int* d_dst, int npair, const T* stage) {
-  if (npair <= 0 || nr <= 0) return hipSuccess;
-  CCArgs<T> a;
-  a.npair = npair; a.nrow = nr; a.ld = ld; a.dst = d_dst; a.src = nullptr; a.table = table + (size_t)r0 * ld; a.stage = const_cast<T*>(stage);
-  hipLaunchKernelGGL((vic_copy_unpack<T>), copy_grid(npair, nr), dim3(64), 0, st, a);
-  return hipGetLastError();
+  return rows_scatter<T>(st, table + (size_t)r0 * ld, ld, nullptr, nr, d_dst, npair, stage);
 }
 
-// every row of table[nrow][ld] on the staged path, rows_per_pass rows at a time through stage[rows_per_pass][npair]
+// every row of table[nrow][ld] on the staged path, per_pass rows at a time through stage[per_pass][npair]
 template <typename T>
 static inline hipError_t copy_staged(hipStream_t st, T* table, size_t ld, int nrow, const int* d_dst, const int* d_src, int npair, T* stage,
-                                     int rows_per_pass) {
-  hipError_t e = hipSuccess;
-  for (int r0 = 0; r0 < nrow && e == hipSuccess; r0 += rows_per_pass) {
-    const int nr = nrow - r0 < rows_per_pass ? nrow - r0 : rows_per_pass;
-    if ((e = copy_pack(st, table, ld, r0, nr, d_src, npair, stage)) == hipSuccess) e = copy_unpack(st, table, ld, r0, nr, d_dst, npair, stage);
-  }
-  return e;
+                                     int per_pass) {
+  return for_row_passes(nrow, per_pass, [&](int r0, int nr) {
+    const hipError_t e = copy_pack<T>(st, table, ld, r0, nr, d_src, npair, stage);
+    return e == hipSuccess ? copy_unpack<T>(st, table, ld, r0, nr, d_dst, npair, stage) : e;
+  });
 }
 
 }  // namespace vic

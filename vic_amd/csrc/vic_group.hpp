@@ -93,8 +93,10 @@ struct vicgpu_group {
   int ncol = 0;
   std::vector<int> cell_col, col_lo;
   // for vicgpu_group_copy_cells, which plans on the whole domain: the caller's CSR lists, the HRU rows a pair of cells must
-  // agree in ([COPY_NKEY][nhru]), and every HRU's shard and id within it
-  std::vector<int> cell_off, cell_list, copy_key, hru_shard, hru_local;
+  // agree in ([COPY_NKEY][nhru])
+  std::vector<int> cell_off, cell_list, copy_key;
+  // every cell's and every HRU's shard and id within it: how a caller's list of columns is split (group_columns)
+  std::vector<int> cell_shard, cell_local, hru_shard, hru_local;
   int nshard() const { return (int)ctx.size(); }
   int c0(int k) const { return bounds[k]; }
   void identity_map() { ncol = ncell; cell_col.clear(); col_lo.assign(bounds.begin(), bounds.end() - 1); }
@@ -117,27 +119,64 @@ static int group_fail(vicgpu_group* g, int code, const std::string& msg) {
   return code;
 }
 
-// The per-HRU table [nrow][nhru] of the caller <-> shard k's [nrow][nhru_k] (its HRUs in its own numbering)
+// The columns pos[0 .. nk) of the caller's values[nrow][n] <-> a shard's packed table [nrow][nk]
 template <typename T>
-static void split_hru_table(const vicgpu_group* g, int k, const T* global, int nrow, std::vector<T>& local) {
-  const std::vector<int>& ids = g->hru[k];
-  const size_t n = ids.size();
-  local.resize((size_t)nrow * n);
+static void take_columns(const T* values, int nrow, size_t n, const std::vector<int>& pos, std::vector<T>& packed) {
+  const size_t nk = pos.size();
+  packed.resize((size_t)nrow * nk);
   for (int r = 0; r < nrow; r++) {
-    const T* src = global + (size_t)r * g->nhru;
-    T* dst = local.data() + (size_t)r * n;
-    for (size_t j = 0; j < n; j++) dst[j] = src[ids[j]];
+    const T* src = values + (size_t)r * n;
+    T* dst = packed.data() + (size_t)r * nk;
+    for (size_t j = 0; j < nk; j++) dst[j] = src[pos[j]];
   }
 }
 template <typename T>
-static void merge_hru_table(const vicgpu_group* g, int k, const std::vector<T>& local, int nrow, T* global) {
-  const std::vector<int>& ids = g->hru[k];
-  const size_t n = ids.size();
+static void put_columns(T* values, int nrow, size_t n, const std::vector<int>& pos, const std::vector<T>& packed) {
+  const size_t nk = pos.size();
   for (int r = 0; r < nrow; r++) {
-    const T* src = local.data() + (size_t)r * n;
-    T* dst = global + (size_t)r * g->nhru;
-    for (size_t j = 0; j < n; j++) dst[ids[j]] = src[j];
+    const T* src = packed.data() + (size_t)r * nk;
+    T* dst = values + (size_t)r * n;
+    for (size_t j = 0; j < nk; j++) dst[pos[j]] = src[j];
   }
+}
+
+// The per-HRU table [nrow][nhru] of the caller <-> shard k's [nrow][nhru_k] (its HRUs in its own numbering)
+template <typename T>
+static void split_hru_table(const vicgpu_group* g, int k, const T* global, int nrow, std::vector<T>& local) {
+  take_columns(global, nrow, (size_t)g->nhru, g->hru[k], local);
+}
+template <typename T>
+static void merge_hru_table(const vicgpu_group* g, int k, const std::vector<T>& local, int nrow, T* global) {
+  put_columns(global, nrow, (size_t)g->nhru, g->hru[k], local);
+}
+
+// A caller's list of n columns, cells (per_cell) or HRUs in the global numbering, by shard: the entries of the list that are
+// shard k's own (pos[k]) and their ids within it (local[k]).  cols == nullptr, the dense form: every column of the shard in
+// pos[k] and no local list -- a shard's cells are a block of the caller's, its HRUs are numbered in the caller's order, so
+// the call stays dense in every shard.  The list has been checked (check_param_update).
+struct GroupColumns {
+  std::vector<std::vector<int>> pos, local;
+  const int* idx(int k) const { return local[k].empty() ? nullptr : local[k].data(); }
+};
+
+static GroupColumns group_columns(const vicgpu_group* g, bool per_cell, int n, const int* cols) {
+  GroupColumns L;
+  const int ns = g->nshard();
+  L.pos.resize(ns); L.local.resize(ns);
+  const std::vector<int>& shard = per_cell ? g->cell_shard : g->hru_shard;
+  const std::vector<int>& local = per_cell ? g->cell_local : g->hru_local;
+  if (cols) {
+    for (int i = 0; i < n; i++) {
+      L.pos[shard[cols[i]]].push_back(i);
+      L.local[shard[cols[i]]].push_back(local[cols[i]]);
+    }
+  } else if (per_cell) {
+    for (int k = 0; k < ns; k++)
+      for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) L.pos[k].push_back(i);
+  } else {
+    L.pos = g->hru;
+  }
+  return L;
 }
 
 static bool group_ready(vicgpu_group* g) {
@@ -238,9 +277,9 @@ int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* 
     if (b[k + 1] == b[k]) return group_fail(g, VICGPU_ERR_ARG, "set_domain: shard " + std::to_string(k) + " gets no cell");
   // shard k: its cells' HRUs in the domain's HRU order, renumbered from 0 (vic_amd/shard.py shard_domain)
   g->hru.assign(ns, std::vector<int>());
-  std::vector<int> shard_of(ncell), new_id(nhru);
+  std::vector<int> shard_of(ncell), cell_id(ncell), new_id(nhru);
   for (int k = 0; k < ns; k++)
-    for (int i = b[k]; i < b[k + 1]; i++) shard_of[i] = k;
+    for (int i = b[k]; i < b[k + 1]; i++) { shard_of[i] = k; cell_id[i] = i - b[k]; }
   for (int h = 0; h < nhru; h++) {
     std::vector<int>& ids = g->hru[shard_of[hpi[(size_t)HPI_CELL * nhru + h]]];
     new_id[h] = (int)ids.size();
@@ -277,6 +316,7 @@ int vicgpu_group_set_domain(vicgpu_group* g, int ncell, int nhru, const double* 
   g->copy_key.resize((size_t)COPY_NKEY * nhru);
   for (int r = 0; r < COPY_NKEY; r++)
     std::copy(hpi + (size_t)COPY_KEY_ROWS[r] * nhru, hpi + (size_t)(COPY_KEY_ROWS[r] + 1) * nhru, g->copy_key.begin() + (size_t)r * nhru);
+  g->cell_shard = shard_of; g->cell_local = cell_id;
   g->hru_local = new_id;
   g->hru_shard.resize(nhru);
   for (int h = 0; h < nhru; h++) g->hru_shard[h] = shard_of[hpi[(size_t)HPI_CELL * nhru + h]];
@@ -540,12 +580,9 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
   if (p.fault != COPY_OK) return group_fail(g, VICGPU_ERR_ARG, copy_fault_text(p));
   if (p.cell.size() == 0) return VICGPU_OK;
   const int ns = g->nshard();
-  std::vector<int> cell_shard(g->ncell), cell_local(g->ncell);
-  for (int k = 0; k < ns; k++)
-    for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) { cell_shard[i] = k; cell_local[i] = i - g->bounds[k]; }
   GroupCopyKind kind[2];           // [0] HRUs, [1] cells
   group_copy_kind(ns, p.hru, g->hru_shard, g->hru_local, kind[0]);
-  group_copy_kind(ns, p.cell, cell_shard, cell_local, kind[1]);
+  group_copy_kind(ns, p.cell, g->cell_shard, g->cell_local, kind[1]);
   // rows per pass of every table: the largest export or import list of its kind within the budget
   const size_t budget = (size_t)g->ctx[0]->tune.copy_stage_mb << 20;
   int rpp[COPY_NTABLE] = {0, 0, 0, 0};
@@ -556,7 +593,7 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
       const GroupCopyKind& K = kind[per_cell ? 1 : 0];
       size_t most = 0;
       for (int k = 0; k < ns; k++) most = std::max(most, std::max(K.exp_n[k], K.imp_n[k]));
-      rpp[t] = copy_rows_per_pass(budget, most, sizeof(*table), nrow);
+      rpp[t] = rows_per_pass(budget, most, sizeof(*table), nrow);
       nrow_of[t] = nrow;
       for (int k = 0; k < ns; k++) {
         exp_bytes[k] = std::max(exp_bytes[k], (size_t)rpp[t] * K.exp_n[k] * sizeof(*table));
@@ -590,10 +627,9 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
     return (int)VICGPU_OK;
   });
   for (int t = 0; t < COPY_NTABLE && r == VICGPU_OK; t++)
-    for (int r0 = 0; r0 < nrow_of[t] && r == VICGPU_OK; r0 += rpp[t]) {
-      const int nr = std::min(rpp[t], nrow_of[t] - r0);
+    r = for_row_passes(nrow_of[t], rpp[t], [&](int r0, int nr) {
       const size_t cap = rpp[t];                       // rows a block is laid out for
-      r = group_each(g, [&](int k) {                   // 1. pack
+      const int packed_all = group_each(g, [&](int k) {      // 1. pack
         vicgpu_ctx* c = g->ctx[k];
         HIPCHK(c, hipSetDevice(c->device));
         const hipError_t packed = copy_table(c, t, what, [&](auto* table, int, size_t ld, bool per_cell) {
@@ -612,8 +648,8 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return (int)VICGPU_OK;
       });
-      if (r != VICGPU_OK) break;
-      r = group_each(g, [&](int s) {                   // 2. fetch and unpack
+      if (packed_all != VICGPU_OK) return packed_all;
+      return group_each(g, [&](int s) {                // 2. fetch and unpack
         vicgpu_ctx* c = g->ctx[s];
         HIPCHK(c, hipSetDevice(c->device));
         const hipError_t unpacked = copy_table(c, t, what, [&](auto* table, int, size_t ld, bool per_cell) {
@@ -638,7 +674,7 @@ int vicgpu_group_copy_cells(vicgpu_group* g, int n, const int* dst_cell, const i
         HIPCHK(c, hipStreamSynchronize(c->stream));    // the next pass packs into the buffers the others have just read
         return (int)VICGPU_OK;
       });
-    }
+    });
   if (r != VICGPU_OK)              // a shard's stream may still hold kernels on the buffers that go now
     for (vicgpu_ctx* c : g->ctx) vicgpu_synchronize(c);
   return r;
@@ -655,43 +691,17 @@ static int group_update_params(vicgpu_group* g, bool per_cell, int nrow, const i
   if (nrow == 0 || n == 0) return VICGPU_OK;
   if (!rows || !values) return group_fail(g, VICGPU_ERR_ARG, "update params: null rows or values");
   const int table_rows = per_cell ? (int)VICGPU_CP_NROW(g->opt.Nnode, g->opt.Nband) : (int)HPD_NROW;
+  const char* name = per_cell ? "update_cell_params" : "update_hru_params";
   const ParamFault f = check_param_update(table_rows, per_cell ? g->ncell : g->nhru, nrow, rows, n, cols);
-  if (f.rule != PARAM_OK)
-    return group_fail(g, VICGPU_ERR_ARG, std::string(per_cell ? "update_cell_params: " : "update_hru_params: ") +
-                                             (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
-  const int ns = g->nshard();
-  // shard k: the entries of the caller's list that are its own (pos) and their ids within it (local); dense: pos only
-  std::vector<std::vector<int>> pos(ns), local(ns);
-  if (cols) {
-    std::vector<int> cell_shard;
-    if (per_cell) {
-      cell_shard.resize(g->ncell);
-      for (int k = 0; k < ns; k++)
-        for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) cell_shard[i] = k;
-    }
-    for (int i = 0; i < n; i++) {
-      const int k = per_cell ? cell_shard[cols[i]] : g->hru_shard[cols[i]];
-      pos[k].push_back(i);
-      local[k].push_back(per_cell ? cols[i] - g->bounds[k] : g->hru_local[cols[i]]);
-    }
-  } else {
-    for (int k = 0; k < ns; k++) {
-      if (per_cell) for (int i = g->bounds[k]; i < g->bounds[k + 1]; i++) pos[k].push_back(i);
-      else pos[k] = g->hru[k];
-    }
-  }
+  if (f.rule != PARAM_OK) return group_fail(g, VICGPU_ERR_ARG, param_fault_message(name, f));
+  const GroupColumns L = group_columns(g, per_cell, n, cols);
   return group_each(g, [&](int k) {
-    const size_t nk = pos[k].size();
+    const size_t nk = L.pos[k].size();
     if (nk == 0) return (int)VICGPU_OK;
-    std::vector<double> v((size_t)nrow * nk);
-    for (int r = 0; r < nrow; r++) {
-      const double* src = values + (size_t)r * n;
-      double* dst = v.data() + (size_t)r * nk;
-      for (size_t j = 0; j < nk; j++) dst[j] = src[pos[k][j]];
-    }
-    const int* idx = cols ? local[k].data() : nullptr;
-    return per_cell ? vicgpu_update_cell_params(g->ctx[k], nrow, rows, (int)nk, idx, v.data())
-                    : vicgpu_update_hru_params(g->ctx[k], nrow, rows, (int)nk, idx, v.data());
+    std::vector<double> v;
+    take_columns(values, nrow, (size_t)n, L.pos[k], v);
+    return per_cell ? vicgpu_update_cell_params(g->ctx[k], nrow, rows, (int)nk, L.idx(k), v.data())
+                    : vicgpu_update_hru_params(g->ctx[k], nrow, rows, (int)nk, L.idx(k), v.data());
   });
 }
 
@@ -725,26 +735,6 @@ int vicgpu_group_get_hru_params(vicgpu_group* g, double* hru_dparams) {
 // before any shard writes; then every shard takes its own columns, rebased, on the group's threads.
 }  // extern "C": the helpers are templates
 
-struct GroupHruLists {
-  std::vector<std::vector<int>> pos, local;    // [shard]: entries of the caller's list that are its own; their ids within it (listed form only)
-};
-
-static GroupHruLists group_hru_lists(const vicgpu_group* g, int n, const int* hrus) {
-  GroupHruLists L;
-  const int ns = g->nshard();
-  L.pos.resize(ns); L.local.resize(ns);
-  if (hrus) {
-    for (int i = 0; i < n; i++) {
-      const int k = g->hru_shard[hrus[i]];
-      L.pos[k].push_back(i);
-      L.local[k].push_back(g->hru_local[hrus[i]]);
-    }
-  } else {
-    for (int k = 0; k < ns; k++) L.pos[k] = g->hru[k];
-  }
-  return L;
-}
-
 // op: ROWS_GET / ROWS_SET / ROWS_ADD of the context entries; INT: the SI table
 template <typename T>
 static int group_state_rows(vicgpu_group* g, const char* name, bool INT, int op, int nrow, const int* rows, int n, const int* hrus, T* values) {
@@ -754,26 +744,21 @@ static int group_state_rows(vicgpu_group* g, const char* name, bool INT, int op,
   if (!rows || !values) return group_fail(g, VICGPU_ERR_ARG, std::string(name) + ": null rows or values");
   const int table_rows = INT ? (int)VICGPU_SI_NROW(g->opt.Nnode) : (int)VICGPU_SD_NROW(g->opt.Nnode);
   const ParamFault f = check_param_update(table_rows, g->nhru, nrow, rows, n, hrus);
-  if (f.rule != PARAM_OK)
-    return group_fail(g, VICGPU_ERR_ARG, std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
-  const GroupHruLists L = group_hru_lists(g, n, hrus);
+  if (f.rule != PARAM_OK) return group_fail(g, VICGPU_ERR_ARG, param_fault_message(name, f));
+  const GroupColumns L = group_columns(g, false, n, hrus);
   return group_each(g, [&](int k) {
     const size_t nk = L.pos[k].size();
     if (nk == 0) return (int)VICGPU_OK;
     std::vector<T> v((size_t)nrow * nk);
-    if (op != ROWS_GET)
-      for (int r = 0; r < nrow; r++)
-        for (size_t j = 0; j < nk; j++) v[(size_t)r * nk + j] = values[(size_t)r * n + L.pos[k][j]];
-    const int* idx = hrus ? L.local[k].data() : nullptr;
+    if (op != ROWS_GET) take_columns(values, nrow, (size_t)n, L.pos[k], v);
+    const int* idx = L.idx(k);
     int rc;
     if constexpr (std::is_same<T, int>::value)
       rc = op == ROWS_GET ? vicgpu_get_state_rows_i(g->ctx[k], nrow, rows, (int)nk, idx, v.data()) : vicgpu_update_state_i(g->ctx[k], nrow, rows, (int)nk, idx, v.data());
     else
       rc = op == ROWS_GET ? vicgpu_get_state_rows(g->ctx[k], nrow, rows, (int)nk, idx, v.data())
                           : vicgpu_update_state(g->ctx[k], nrow, rows, (int)nk, idx, v.data(), op == ROWS_ADD ? VICGPU_STATE_ADD : VICGPU_STATE_SET);
-    if (rc == VICGPU_OK && op == ROWS_GET)       // the shards' positions in the caller's list are disjoint
-      for (int r = 0; r < nrow; r++)
-        for (size_t j = 0; j < nk; j++) values[(size_t)r * n + L.pos[k][j]] = v[(size_t)r * nk + j];
+    if (rc == VICGPU_OK && op == ROWS_GET) put_columns(values, nrow, (size_t)n, L.pos[k], v);      // the shards' positions in the caller's list are disjoint
     return rc;
   });
 }
@@ -805,13 +790,12 @@ int vicgpu_group_derive_soil_state(vicgpu_group* g, int n, const int* hrus, int 
   if (rule == DERIVE_UNSUPPORTED) return group_fail(g, VICGPU_ERR_UNSUPPORTED, "derive_soil_state: VICGPU_DERIVE_CAP_MOIST with GLACIER_DYNAMICS");
   if (n == 0) return VICGPU_OK;
   const ParamFault f = check_param_update(0, g->nhru, 0, nullptr, n, hrus);
-  if (f.rule != PARAM_OK)
-    return group_fail(g, VICGPU_ERR_ARG, std::string("derive_soil_state: ") + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule));
-  const GroupHruLists L = group_hru_lists(g, n, hrus);
+  if (f.rule != PARAM_OK) return group_fail(g, VICGPU_ERR_ARG, param_fault_message("derive_soil_state", f));
+  const GroupColumns L = group_columns(g, false, n, hrus);
   return group_each(g, [&](int k) {
     const size_t nk = L.pos[k].size();
     if (nk == 0) return (int)VICGPU_OK;
-    return vicgpu_derive_soil_state(g->ctx[k], (int)nk, hrus ? L.local[k].data() : nullptr, what);
+    return vicgpu_derive_soil_state(g->ctx[k], (int)nk, L.idx(k), what);
   });
 }
 

@@ -85,6 +85,22 @@ struct Event {
   hipEvent_t e = nullptr;
 };
 
+// The event pair of an entry that reports its time on a stream under VICGPU_STATS.  Off (create(false)), it holds no event and
+// every call is a no-op that succeeds: an entry creates it before its first upload and calls it unconditionally.
+struct StreamTimer {
+  hipError_t create(bool enabled) {
+    on = enabled;
+    hipError_t e = on ? t0.create() : hipSuccess;
+    if (on && e == hipSuccess) e = t1.create();
+    return e;
+  }
+  hipError_t begin(hipStream_t st) { return on ? hipEventRecord(t0, st) : hipSuccess; }
+  hipError_t end(hipStream_t st) { return on ? hipEventRecord(t1, st) : hipSuccess; }
+  bool elapsed(float* ms) { return on && hipEventElapsedTime(ms, t0, t1) == hipSuccess; }      // once the stream has passed end()
+  Event t0, t1;
+  bool on = false;
+};
+
 // A non-blocking stream of its own, or a borrowed one (vicgpu_set_stream), which is never destroyed here
 struct Stream {
   Stream() = default;

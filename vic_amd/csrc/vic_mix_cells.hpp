@@ -15,8 +15,8 @@
 //                      tile's rows; a term's loads are all issued, and the next term's column resolved, before the dependent
 //                      adds: the row tile gives MX_ROWS independent chains.  Accumulators in registers, no LDS, no scratch,
 //                      plain vector loads and stores.  A zero weight still reads its operand.
-//   mix_cells_staged   the rows go in passes of at most rows_per_pass rows (copy_rows_per_pass) through stage[..][n], and each
-//                      pass is scattered into table[rows[k]][hru] by state_scatter (SET).  The result always goes through the
+//   mix_cells_staged   the rows go in passes of at most per_pass rows (rows_per_pass, vic_rows.hpp) through stage[..][n], and each
+//                      pass is scattered into table[rows[k]][hru] by rows_scatter (SET).  The result always goes through the
 //                      stage: every source is read before any destination is written.  A row is read and written within its
 //                      own pass, so the result does not depend on the budget.
 // The kernel trusts its indices: plan_cell_mix has checked them.
@@ -26,9 +26,8 @@
 #include <cstddef>
 #include <string>
 #include <vector>
-#include "vic_copy_cells.hpp"
-#include "vic_params.hpp"
-#include "vic_state_update.hpp"
+#include "vic_copy_cells.hpp"      // the pair rule: copy_pair_fault, copy_pair_fault_text
+#include "vic_rows.hpp"
 
 namespace vic {
 
@@ -119,7 +118,7 @@ static inline std::string mix_fault_text(const MixPlan& p) {
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
-constexpr int MX_ROWS = 8;         // rows per launch row (blockIdx.y): the independent accumulator chains of a lane
+constexpr int MX_ROWS = ROW_TILE;  // rows per launch row (blockIdx.y): the independent accumulator chains of a lane
 
 struct MXArgs {
   int n, nrow;                     // destination HRUs; rows of this pass, counted from the entry `rows` and the row `stage` point to
@@ -194,16 +193,13 @@ static inline hipError_t mix_cells_pass(hipStream_t st, const double* table, siz
   return hipGetLastError();
 }
 
-// every listed row, rows_per_pass rows at a time through stage[rows_per_pass][n]: the mix of a pass, then its scatter into
+// every listed row, per_pass rows at a time through stage[per_pass][n]: the mix of a pass, then its scatter into
 // table[rows[k]][hru].  The scatter of a pass follows its mix on the stream, and the next pass reads other rows.
-static inline hipError_t mix_cells_staged(hipStream_t st, double* table, size_t ld, const MixLists& l, int nrow, int n, double* stage, int rows_per_pass) {
-  hipError_t e = hipSuccess;
-  for (int r0 = 0; r0 < nrow && e == hipSuccess; r0 += rows_per_pass) {
-    const int nr = nrow - r0 < rows_per_pass ? nrow - r0 : rows_per_pass;
-    e = mix_cells_pass(st, table, ld, l, r0, nr, n, stage);
-    if (e == hipSuccess) e = state_scatter(st, table, ld, l.rows + r0, nr, l.hru, n, stage, false);
-  }
-  return e;
+static inline hipError_t mix_cells_staged(hipStream_t st, double* table, size_t ld, const MixLists& l, int nrow, int n, double* stage, int per_pass) {
+  return for_row_passes(nrow, per_pass, [&](int r0, int nr) {
+    const hipError_t e = mix_cells_pass(st, table, ld, l, r0, nr, n, stage);
+    return e == hipSuccess ? rows_scatter<double>(st, table, ld, l.rows + r0, nr, l.hru, n, stage) : e;
+  });
 }
 
 }  // namespace vic

@@ -1,32 +1,23 @@
 // vic_state_update.hpp — model state read and changed in place, row by row, and its dependent soil rows re-derived on the
 // device (vicgpu_get_state_rows / vicgpu_update_state / vicgpu_derive_soil_state, include/vicgpu.h): the analysis update of an
-// ensemble loop, and the tail of a restart.  The check of a call on the host, the kernels for gfx950 and their launchers.
-// Nothing here knows a context: a table is a [..][ld] array, the lists are row and column indices, the parameter tables are
-// passed in (as in vic_params.hpp).
+// ensemble loop, and the tail of a restart.  The check of a derive on the host, the derive kernel for gfx950 and its launcher.
+// Reading and writing the rows is vic_rows.hpp as it stands: check_param_update, then rows_get_staged (vic_rows_gather) or
+// rows_put_staged (vic_rows_scatter, SET or ADD) on the SD or the SI table.  Nothing here knows a context: a table is a
+// [..][ld] array, the lists are row and column indices, the parameter tables are passed in (as in vic_params.hpp).
 //
-//   check_param_update   (vic_params.hpp) rows and columns of a call; check_derive_what the stage bits of a derive.
-//   vic_state_gather<T>  values[k][i] = table[rows[k]][idx[i]]: the mirror image of vic_param_scatter.  A lane is one listed
-//                        column i and a tile of PU_ROWS rows (blockIdx.y); the tile's words are all loaded before they are
-//                        stored, consecutive lanes write consecutive words of a row of `values`.  double and int.
-//   vic_state_scatter<T, ADD>
-//                        table[rows[k]][idx[i]] = values[k][i] (ADD: old + value, one rounded add) for what vic_param_scatter
-//                        does not cover: int tables and ADD.  SET on doubles is vic_param_scatter itself.
+//   check_derive_what    the stage bits of a derive.
 //   vic_derive_soil_state<NN>
 //                        lane = listed HRU.  The tail of initialize_model_state.c for one HRU, stage by stage, through the
 //                        device functions the step itself calls (vic_soil.hpp): the moisture cap (:397-434),
 //                        distribute_node_moisture_properties (:712), estimate_layer_ice_content(_quick_flux) (:728-732),
 //                        find_0_degree_fronts (:736-737).  A stage's rows are stored before the next stage starts, and a
 //                        later stage reads what the earlier ones left.  Plain vector loads and stores, no LDS.
-//   state_gather_staged / state_scatter_staged
-//                        the values of a call go through a device stage in row passes of at most rows_per_pass rows
-//                        (copy_rows_per_pass, vic_copy_cells.hpp); a row is moved within its own pass, so the result does not
-//                        depend on the budget.
-// The kernels trust their indices: the check has seen them.
+// The kernel trusts its indices: the check has seen them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "vic_hru_io.hpp"
-#include "vic_params.hpp"
+#include "vic_rows.hpp"
 
 namespace vic {
 
@@ -41,52 +32,6 @@ static inline int check_derive_what(int what, int glacier_dynamics) {
   // the reference keeps the moisture above max_moist in cell.excess_moist (initialize_model_state.c:410), which no table carries
   if ((what & VICGPU_DERIVE_CAP_MOIST) && glacier_dynamics) return DERIVE_UNSUPPORTED;
   return DERIVE_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ gather / scatter kernels
-template <typename T>
-struct SUArgs {
-  int n, nrow;                     // listed columns; rows of this pass, counted from the entry `rows` and the row `values` point to
-  size_t ld;                       // columns per row of the table
-  const int* rows;                 // [nrow] table rows
-  const int* idx;                  // [n] table columns, or null: column i
-  T* values;                       // [nrow][n]: written by the gather, read by the scatter
-  T* table;                        // [..][ld]
-};
-
-template <typename T>
-__global__ __launch_bounds__(64) void vic_state_gather(const SUArgs<T> a) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= a.n) return;
-  const int r0 = blockIdx.y * PU_ROWS;
-  const size_t col = a.idx ? (size_t)a.idx[i] : (size_t)i;
-  T* __restrict__ out = a.values + (size_t)r0 * a.n + i;
-  T v[PU_ROWS];
-#pragma unroll
-  for (int k = 0; k < PU_ROWS; k++)
-    if (r0 + k < a.nrow) v[k] = a.table[(size_t)a.rows[r0 + k] * a.ld + col];
-#pragma unroll
-  for (int k = 0; k < PU_ROWS; k++)
-    if (r0 + k < a.nrow) out[(size_t)k * a.n] = v[k];
-}
-
-template <typename T, bool ADD>
-__global__ __launch_bounds__(64) void vic_state_scatter(const SUArgs<T> a) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= a.n) return;
-  const int r0 = blockIdx.y * PU_ROWS;
-  const size_t col = a.idx ? (size_t)a.idx[i] : (size_t)i;
-  const T* __restrict__ in = a.values + (size_t)r0 * a.n + i;
-  T v[PU_ROWS];
-#pragma unroll
-  for (int k = 0; k < PU_ROWS; k++)
-    if (r0 + k < a.nrow) {
-      v[k] = in[(size_t)k * a.n];
-      if (ADD) v[k] = a.table[(size_t)a.rows[r0 + k] * a.ld + col] + v[k];
-    }
-#pragma unroll
-  for (int k = 0; k < PU_ROWS; k++)
-    if (r0 + k < a.nrow) a.table[(size_t)a.rows[r0 + k] * a.ld + col] = v[k];
 }
 
 // ------------------------------------------------------------------------------------------------ derive kernel
@@ -190,69 +135,6 @@ __global__ __launch_bounds__(64) void vic_derive_soil_state(const DSArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ launchers (host)
-template <typename T>
-static inline SUArgs<T> state_rows_args(T* table, size_t ld, const int* d_rows, int nr, const int* d_idx, int n, T* d_values) {
-  SUArgs<T> a;
-  a.n = n; a.nrow = nr; a.ld = ld; a.rows = d_rows; a.idx = d_idx; a.values = d_values; a.table = table;
-  return a;
-}
-
-static inline dim3 state_rows_grid(int n, int nr) { return dim3((unsigned)((n + 63) / 64), (unsigned)((nr + PU_ROWS - 1) / PU_ROWS)); }
-
-// d_values[nr][n] = rows d_rows[0 .. nr) of table[..][ld], columns d_idx[0 .. n) (null: 0 .. n)
-template <typename T>
-static inline hipError_t state_gather(hipStream_t st, const T* table, size_t ld, const int* d_rows, int nr, const int* d_idx, int n, T* d_values) {
-  if (n <= 0 || nr <= 0) return hipSuccess;
-  const SUArgs<T> a = state_rows_args<T>(const_cast<T*>(table), ld, d_rows, nr, d_idx, n, d_values);
-  hipLaunchKernelGGL(vic_state_gather<T>, state_rows_grid(n, nr), dim3(64), 0, st, a);
-  return hipGetLastError();
-}
-
-static inline hipError_t state_scatter(hipStream_t st, double* table, size_t ld, const int* d_rows, int nr, const int* d_idx, int n,
-                                       const double* d_values, bool add) {
-  if (!add) return param_scatter(st, table, ld, d_rows, nr, d_idx, n, d_values);
-  if (n <= 0 || nr <= 0) return hipSuccess;
-  const SUArgs<double> a = state_rows_args<double>(table, ld, d_rows, nr, d_idx, n, const_cast<double*>(d_values));
-  hipLaunchKernelGGL((vic_state_scatter<double, true>), state_rows_grid(n, nr), dim3(64), 0, st, a);
-  return hipGetLastError();
-}
-
-static inline hipError_t state_scatter(hipStream_t st, int* table, size_t ld, const int* d_rows, int nr, const int* d_idx, int n,
-                                       const int* d_values, bool) {
-  if (n <= 0 || nr <= 0) return hipSuccess;
-  const SUArgs<int> a = state_rows_args<int>(table, ld, d_rows, nr, d_idx, n, const_cast<int*>(d_values));
-  hipLaunchKernelGGL((vic_state_scatter<int, false>), state_rows_grid(n, nr), dim3(64), 0, st, a);
-  return hipGetLastError();
-}
-
-// The listed rows into values[nrow][n] of the host through stage[rows_per_pass][n].  Every download waits for the stream: the
-// values are in place when this returns.
-template <typename T>
-static inline hipError_t state_gather_staged(hipStream_t st, const T* table, size_t ld, const int* d_rows, int nrow, const int* d_idx, int n,
-                                             T* values, T* stage, int rows_per_pass) {
-  hipError_t e = hipSuccess;
-  for (int r0 = 0; r0 < nrow && e == hipSuccess; r0 += rows_per_pass) {
-    const int nr = nrow - r0 < rows_per_pass ? nrow - r0 : rows_per_pass;
-    e = state_gather<T>(st, table, ld, d_rows + r0, nr, d_idx, n, stage);
-    if (e == hipSuccess) e = copy_on(st, values + (size_t)r0 * n, stage, sizeof(T) * nr * n, hipMemcpyDeviceToHost);
-  }
-  return e;
-}
-
-// values[nrow][n] of the host into the listed rows.  Every upload waits for the stream, and so for the pass before it:
-// `values` may be reused when this returns, the last kernel may still be running.
-template <typename T>
-static inline hipError_t state_scatter_staged(hipStream_t st, T* table, size_t ld, const int* d_rows, int nrow, const int* d_idx, int n,
-                                              const T* values, T* stage, int rows_per_pass, bool add) {
-  hipError_t e = hipSuccess;
-  for (int r0 = 0; r0 < nrow && e == hipSuccess; r0 += rows_per_pass) {
-    const int nr = nrow - r0 < rows_per_pass ? nrow - r0 : rows_per_pass;
-    e = copy_on(st, stage, values + (size_t)r0 * n, sizeof(T) * nr * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = state_scatter(st, table, ld, d_rows + r0, nr, d_idx, n, stage, add);
-  }
-  return e;
-}
-
 template <int NN>
 static inline hipError_t derive_soil_state_nn(hipStream_t st, const DSArgs& a) {
   hipLaunchKernelGGL(vic_derive_soil_state<NN>, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, st, a);

@@ -9,13 +9,16 @@
 //   vic_aux_kernels.hpp  glacier fit, derived cell rows, test hooks, vic_cell_reduce, state records, forcing derivation
 //   vic_records.hpp      vic_out_pack_reset: the end of an output record (vicgpu_run_records); vic_out_group_reduce: its
 //                        reduction over cell groups (vicgpu_records_set_groups)
-//   vic_copy_cells.hpp   vicgpu_copy_cells: the host planning of a copy between cells, vic_copy_direct / _pack / _unpack
-//   vic_params.hpp       vicgpu_update_cell_params / _hru_params: the host check of an update, vic_param_scatter and the
-//                        listed-cell forms of the derive kernels
-//   vic_state_update.hpp vicgpu_get_state_rows / _update_state / _derive_soil_state: vic_state_gather / _scatter on listed
-//                        state rows and vic_derive_soil_state, the tail of initialize_model_state for listed HRUs
+//   vic_rows.hpp         listed rows and columns of a table through a budgeted stage: the host check of the lists,
+//                        vic_rows_gather / _scatter, the pass loop; shared by the four headers below
+//   vic_copy_cells.hpp   vicgpu_copy_cells: the host planning of a copy between cells, vic_copy_direct, the staged path
+//   vic_params.hpp       vicgpu_update_cell_params / _hru_params: the owner cells of listed HRUs and the listed-cell forms
+//                        of the derive kernels
+//   vic_state_update.hpp vicgpu_get_state_rows / _update_state / _derive_soil_state: vic_derive_soil_state, the tail of
+//                        initialize_model_state for listed HRUs
 //   vic_mix_cells.hpp    vicgpu_mix_cells: the host planning of a linear combination across cells and vic_mix_cells
-//   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers
+//   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers; the
+//                        VICGPU_STATS timer of an entry
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
 //   vic_pipeline.hpp     vicgpu_ctx, Tuning, Domain, FdChunk and the steps that build them, the launchers, fd_step, the read-backs
 //   vic_group.hpp        the device group (include/vicgpu_group.h): host code on top of the entries below
@@ -45,6 +48,7 @@
 #include "vic_kernels.hpp"
 #include "vic_aux_kernels.hpp"
 #include "vic_records.hpp"
+#include "vic_rows.hpp"
 #include "vic_copy_cells.hpp"
 #include "vic_params.hpp"
 #include "vic_state_update.hpp"
@@ -898,7 +902,7 @@ int vicgpu_copy_cells(vicgpu_ctx* c, int n, const int* dst_cell, const int* src_
     for (int t = 0; t < COPY_NTABLE; t++)
       HIPIGN(copy_table(c, t, what, [&](auto* table, int nrow, size_t, bool per_cell) {
         const size_t np = per_cell ? nc : nh, eb = sizeof(*table);
-        bytes = std::max(bytes, (size_t)copy_rows_per_pass(budget, np, eb, nrow) * np * eb);
+        bytes = std::max(bytes, (size_t)rows_per_pass(budget, np, eb, nrow) * np * eb);
         return hipSuccess;
       }));
     HIPCHK(c, stage.alloc((bytes + 7) / 8));
@@ -909,10 +913,10 @@ int vicgpu_copy_cells(vicgpu_ctx* c, int n, const int* dst_cell, const int* src_
   h.insert(h.end(), p.cell.dst.begin(), p.cell.dst.end()); h.insert(h.end(), p.cell.src.begin(), p.cell.src.end());
   // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
   // `done` event, step_impl) and precedes every step queued later: the copy is queued there
-  Event t0, t1;                    // tuning (VICGPU_STATS): the kernels' own time
-  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  StreamTimer timer;               // tuning (VICGPU_STATS): the kernels' own time
+  HIPCHK(c, timer.create(c->tune.stats));
   HIPCHK(c, idx.upload(c->stream, h.data()));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, timer.begin(c->stream));
   size_t moved = 0;                // bytes the tables take
   for (int t = 0; t < COPY_NTABLE; t++) {
     const hipError_t queued = copy_table(c, t, what, [&](auto* table, int nrow, size_t ld, bool per_cell) {
@@ -922,14 +926,14 @@ int vicgpu_copy_cells(vicgpu_ctx* c, int n, const int* dst_cell, const int* src_
       const int* src = dst + np;
       moved += sizeof(T) * nrow * np;
       if (p.direct) return copy_direct<T>(c->stream, table, ld, nrow, dst, src, np);
-      return copy_staged<T>(c->stream, table, ld, nrow, dst, src, np, reinterpret_cast<T*>(stage.get()), copy_rows_per_pass(budget, np, sizeof(T), nrow));
+      return copy_staged<T>(c->stream, table, ld, nrow, dst, src, np, reinterpret_cast<T*>(stage.get()), rows_per_pass(budget, np, sizeof(T), nrow));
     });
     HIPCHK(c, queued);
   }
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, timer.end(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the pairs and the stage are released when the call returns
   float ms = 0;
-  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+  if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] copy_cells: %d cell pairs, %d HRU pairs, %s, %zu bytes written: %.4f ms on the device\n", nc, nh,
             p.direct ? "direct" : "staged", moved, ms);
   return VICGPU_OK;
@@ -951,7 +955,7 @@ static int update_params_impl(vicgpu_ctx* c, bool per_cell, int nrow, const int*
   // every row and column is checked here, before the first write
   const ParamFault f = check_param_update(table_rows, ncol, nrow, rows, n, cols);
   if (f.rule != PARAM_OK) {
-    c->err = std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    c->err = param_fault_message(name, f);
     return VICGPU_ERR_ARG;
   }
   // the cells whose tree-line rows follow: the listed cells, or the owners of the listed HRUs; with a dense call, all
@@ -963,7 +967,7 @@ static int update_params_impl(vicgpu_ctx* c, bool per_cell, int nrow, const int*
   DevBuf<int> lists;
   DevBuf<double> stage;
   HIPCHK(c, lists.alloc((size_t)nrow + nlist + owners.size()));
-  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
+  const int rpp = rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
   HIPCHK(c, stage.alloc((size_t)rpp * n));
   std::vector<int> h(rows, rows + nrow);
   if (cols) h.insert(h.end(), cols, cols + n);
@@ -973,29 +977,29 @@ static int update_params_impl(vicgpu_ctx* c, bool per_cell, int nrow, const int*
   const int* d_owners = lists.get() + nrow + nlist;
   // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
   // `done` event, step_impl) and precedes every step queued later: the update is queued there
-  Event t0, t1;                    // tuning (VICGPU_STATS): the call's time on the stream, uploads of the passes included
-  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  StreamTimer timer;               // tuning (VICGPU_STATS): the call's time on the stream, uploads of the passes included
+  HIPCHK(c, timer.create(c->tune.stats));
   HIPCHK(c, lists.upload(c->stream, h.data()));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, timer.begin(c->stream));
   int nderived = 0;
   if (per_cell) {
-    HIPCHK(c, param_scatter_staged(c->stream, d.d_cp, (size_t)d.ncell, d_rows, nrow, d_cols, n, values, stage, rpp));
+    HIPCHK(c, rows_put_staged<double>(c->stream, d.d_cp, (size_t)d.ncell, d_rows, nrow, d_cols, n, values, stage, rpp));
     HIPCHK(c, derive_cell_params_listed(c->stream, d.d_cp, d.ncell, Nn, Nb, d_cols, n));
     if (tree)
       HIPCHK(c, derive_tree_adjust_listed(c->stream, d.d_cp, d.ncell, d.nhru, Nn, Nb, d.d_cell_off, d.d_cell_list, d.d_hpi, d.d_hpd, c->d_veglib, d_cols, n));
     nderived = n;
   } else {
-    HIPCHK(c, param_scatter_staged(c->stream, d.d_hpd, (size_t)d.nhru, d_rows, nrow, d_cols, n, values, stage, rpp));
+    HIPCHK(c, rows_put_staged<double>(c->stream, d.d_hpd, (size_t)d.nhru, d_rows, nrow, d_cols, n, values, stage, rpp));
     if (tree) {
       nderived = cols ? (int)owners.size() : d.ncell;
       HIPCHK(c, derive_tree_adjust_listed(c->stream, d.d_cp, d.ncell, d.nhru, Nn, Nb, d.d_cell_off, d.d_cell_list, d.d_hpi, d.d_hpd, c->d_veglib,
                                           cols ? d_owners : nullptr, nderived));
     }
   }
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, timer.end(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
   float ms = 0;
-  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+  if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] %s: %d rows x %d %s, %s, %d passes, %zu bytes written, rows re-derived for %d cells: %.4f ms on the stream\n", name,
             nrow, n, per_cell ? "cells" : "HRUs", cols ? "listed" : "dense", (nrow + rpp - 1) / rpp, sizeof(double) * nrow * n, nderived, ms);
   return VICGPU_OK;
@@ -1039,14 +1043,14 @@ static int state_rows_impl(vicgpu_ctx* c, const char* name, DevBuf<T> Domain::*t
   // every row and column is checked here, before the first write
   const ParamFault f = check_param_update(table_rows, d.nhru, nrow, rows, n, hrus);
   if (f.rule != PARAM_OK) {
-    c->err = std::string(name) + ": " + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    c->err = param_fault_message(name, f);
     return VICGPU_ERR_ARG;
   }
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf<int> lists;
   DevBuf<T> stage;
   HIPCHK(c, lists.alloc((size_t)nrow + (hrus ? (size_t)n : 0)));
-  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(T), nrow);
+  const int rpp = rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(T), nrow);
   HIPCHK(c, stage.alloc((size_t)rpp * n));
   std::vector<int> h(rows, rows + nrow);
   if (hrus) h.insert(h.end(), hrus, hrus + n);
@@ -1054,17 +1058,17 @@ static int state_rows_impl(vicgpu_ctx* c, const char* name, DevBuf<T> Domain::*t
   const int* d_hrus = hrus ? lists.get() + nrow : nullptr;
   // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
   // `done` event, step_impl) and precedes every step queued later
-  Event t0, t1;                    // tuning (VICGPU_STATS): the call's time on the stream, the copies of the passes included
-  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  StreamTimer timer;               // tuning (VICGPU_STATS): the call's time on the stream, the copies of the passes included
+  HIPCHK(c, timer.create(c->tune.stats));
   HIPCHK(c, lists.upload(c->stream, h.data()));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, timer.begin(c->stream));
   T* tab = (d.*table).get();
-  if (op == ROWS_GET) HIPCHK(c, state_gather_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp));
-  else HIPCHK(c, state_scatter_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp, op == ROWS_ADD));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  if (op == ROWS_GET) HIPCHK(c, rows_get_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp));
+  else HIPCHK(c, rows_put_staged<T>(c->stream, tab, (size_t)d.nhru, d_rows, nrow, d_hrus, n, values, stage, rpp, op == ROWS_ADD));
+  HIPCHK(c, timer.end(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
   float ms = 0;
-  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+  if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] %s: %s, %d rows x %d HRUs, %s, %d passes, %zu bytes: %.4f ms on the stream\n", name,
             op == ROWS_GET ? "get" : op == ROWS_SET ? "set" : "add", nrow, n, hrus ? "listed" : "dense", (nrow + rpp - 1) / rpp, sizeof(T) * nrow * n, ms);
   return VICGPU_OK;
@@ -1106,24 +1110,24 @@ int vicgpu_derive_soil_state(vicgpu_ctx* c, int n, const int* hrus, int what) {
   Domain& d = c->dom;
   const ParamFault f = check_param_update(0, d.nhru, 0, nullptr, n, hrus);
   if (f.rule != PARAM_OK) {
-    c->err = std::string("derive_soil_state: ") + (f.index >= 0 ? "entry " + std::to_string(f.index) + ": " : "") + param_fault_text(f.rule);
+    c->err = param_fault_message("derive_soil_state", f);
     return VICGPU_ERR_ARG;
   }
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf<int> list;
   if (hrus) HIPCHK(c, list.alloc(n));
-  Event t0, t1;                    // tuning (VICGPU_STATS): the kernel's own time
-  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  StreamTimer timer;               // tuning (VICGPU_STATS): the kernel's own time
+  HIPCHK(c, timer.create(c->tune.stats));
   if (hrus) HIPCHK(c, list.upload(c->stream, hrus));
   DSArgs a{};
   a.o = c->o; a.ncell = d.ncell; a.nhru = d.nhru; a.n = n; a.what = what; a.hrus = hrus ? list.get() : nullptr;
   a.cp = d.d_cp; a.hpi = d.d_hpi; a.hpd = d.d_hpd; a.sd = d.d_sd; a.si = d.d_si; a.flux = d.d_flux; a.cell_err = d.d_cell_err;
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, timer.begin(c->stream));
   HIPCHK(c, derive_soil_state(c->stream, a));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, timer.end(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the list is released when the call returns
   float ms = 0;
-  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+  if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] derive_soil_state: %d HRUs, %s, stages %d: %.4f ms on the device\n", n, hrus ? "listed" : "dense", what, ms);
   return VICGPU_OK;
 }
@@ -1152,15 +1156,15 @@ int vicgpu_mix_cells(vicgpu_ctx* c, int nrow, const int* rows, int ndst, const i
   DevBuf<double> weights, stage;
   HIPCHK(c, lists.alloc((size_t)nrow + 3 * (size_t)n + (size_t)ndst + 1 + (size_t)nnz));
   HIPCHK(c, weights.alloc((size_t)nnz));
-  const int rpp = copy_rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
+  const int rpp = rows_per_pass((size_t)c->tune.copy_stage_mb << 20, (size_t)n, sizeof(double), nrow);
   HIPCHK(c, stage.alloc((size_t)rpp * n));
   MixLists l;
   l.rows = lists.get(); l.hru = l.rows + nrow; l.dst_index = l.hru + n; l.pos = l.dst_index + n; l.term_off = l.pos + n;
   l.term_cell = l.term_off + ndst + 1; l.term_weight = weights.get(); l.cell_off = d.d_cell_off; l.cell_list = d.d_cell_list;
   // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
   // `done` event, step_impl) and precedes every step queued later: the mix is queued there
-  Event t0, t1;                    // tuning (VICGPU_STATS): the kernels' own time
-  if (c->tune.stats) { HIPCHK(c, t0.create()); HIPCHK(c, t1.create()); }
+  StreamTimer timer;               // tuning (VICGPU_STATS): the kernels' own time
+  HIPCHK(c, timer.create(c->tune.stats));
   const size_t un = (size_t)n, at_hru = (size_t)nrow, at_off = at_hru + 3 * un, at_cell = at_off + (size_t)ndst + 1;
   HIPCHK(c, lists.upload(c->stream, rows, 0, (size_t)nrow));
   HIPCHK(c, lists.upload(c->stream, p.hru.data(), at_hru, un));
@@ -1169,12 +1173,12 @@ int vicgpu_mix_cells(vicgpu_ctx* c, int nrow, const int* rows, int ndst, const i
   HIPCHK(c, lists.upload(c->stream, term_off, at_off, (size_t)ndst + 1));
   HIPCHK(c, lists.upload(c->stream, term_cell, at_cell, (size_t)nnz));
   HIPCHK(c, weights.upload(c->stream, term_weight));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t0, c->stream));
+  HIPCHK(c, timer.begin(c->stream));
   HIPCHK(c, mix_cells_staged(c->stream, d.d_sd, (size_t)d.nhru, l, nrow, n, stage, rpp));
-  if (c->tune.stats) HIPCHK(c, hipEventRecord(t1, c->stream));
+  HIPCHK(c, timer.end(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
   float ms = 0;
-  if (c->tune.stats && hipEventElapsedTime(&ms, t0, t1) == hipSuccess)
+  if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] mix_cells: %d destinations, %d HRUs, %d terms, %d rows, %d passes, %zu bytes written: %.4f ms on the device\n", ndst, n,
             nnz, nrow, (nrow + rpp - 1) / rpp, sizeof(double) * nrow * n, ms);
   return VICGPU_OK;
