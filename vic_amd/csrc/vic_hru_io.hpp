@@ -50,9 +50,9 @@ struct KArgs {
   int gcount;
   // finite-difference pipeline only (null otherwise)
   unsigned long long* ctx;          // parked per-HRU context, [hru / 64][word][hru % 64]
-  double* pin;                      // profile item blocks [nhru][Nn][PREC]
+  double* pin;                      // profile item blocks [nhru][item_stride(Nn)] (vic_layout.hpp)
   double* ts;                       // trial surface temperature [nhru]
-  double* pout;                     // profile solutions [nhru][pout_hru_stride(Nn)] (two records + their keys)
+  double* pout;                     // profile solutions [nhru][pout_hru_stride(Nn)] (two keyed records)
   int* pslot;                       // [nhru] record the next profile solve writes
   int* hstate;                      // [nhru] 0 idle, 1 residual evaluation pending, 2 root found: stage kernel's turn
   int* list;                        // work list the stage kernel appends to (NBUCKET segments of list_cap entries)

@@ -207,14 +207,14 @@ __global__ __launch_bounds__(64) void vic_profile_solve_implicit(const vic::PArg
           hru = profile_pick(a, bcount, slot);
           S.NOFLUX = a.NOFLUX; S.EXP_TRANS = a.EXP_TRANS;
           S.n = a.NOFLUX ? Nn - 1 : Nn - 2;
-          const double* __restrict__ blk = a.pin + (size_t)hru * Nn * PREC;
+          const double* __restrict__ blk = item_block(a.pin, (size_t)hru, Nn);
           const double* __restrict__ im = x.pimp + (size_t)hru * Nn * PIMP;
           S.deltat = im[PI_ICE];                                    // node 0 (a boundary value) has no ice term: its slot carries delta_t
           const int cell = x.hpi[(size_t)HPI_CELL * x.nhru + hru];
           CellView cv{x.cell_params, x.ncell, cell, Nn, x.Nband};
           for (int q = 0; q < ImplicitSolver::M; q++) {
             const bool in = q < Nn;
-            S.T0[q] = in ? ((q == 0) ? a.ts[hru] : blk[q * PREC + PR_T0]) : 0.0;
+            S.T0[q] = in ? ((q == 0) ? a.ts[hru] : blk[item_t0(q)]) : 0.0;
             S.moist[q] = in ? im[q * PIMP + PI_MOIST] : 0.0; S.ice[q] = in ? im[q * PIMP + PI_ICE] : 0.0;
             S.kappa[q] = in ? im[q * PIMP + PI_KAPPA] : 0.0; S.Cs[q] = in ? im[q * PIMP + PI_CS] : 0.0;
             S.mmn[q] = in ? cv.node(CPN_MAX_MOIST, q) : 0.0; S.bub[q] = in ? cv.node(CPN_BUBBLE, q) : 0.0; S.ex[q] = in ? cv.node(CPN_EXPT, q) : 0.0;
@@ -244,24 +244,23 @@ __global__ __launch_bounds__(64) void vic_profile_solve_implicit(const vic::PArg
       k++;
       if (conv) {
         const int ps = a.pslot[hru];
-        double* __restrict__ rec = a.pout + (size_t)hru * pout_hru_stride(Nn) + ps * pout_stride(Nn);
+        double* __restrict__ rec = pout_rec(a.pout, (size_t)hru, Nn, ps);
         // the flags of the root find's most recent explicit solve (or none)
         const int le = x.lastexp[hru];
         unsigned long long meta = 1ull << 32;                  // ok, no fallback flags
         if (le >= 0) {
-          const double* __restrict__ src = a.pout + (size_t)hru * pout_hru_stride(Nn) + le * pout_stride(Nn);
-          meta = (unsigned long long)__double_as_longlong(src[Nn]) | (1ull << 32);
+          const double* __restrict__ src = pout_rec(a.pout, (size_t)hru, Nn, le);
+          meta = (unsigned long long)__double_as_longlong(src[rec_flag()]) | (1ull << 32);
           if (le != ps)
-            for (int q = 0; q < (Nn + 1) / 2; q++) rec[Nn + 1 + q] = src[Nn + 1 + q];     // the packed int counters
+            for (int q = 0; q < (Nn + 1) / 2; q++) rec[rec_cnt(Nn) + q] = src[rec_cnt(Nn) + q];     // the packed int counters
         } else {
-          int* __restrict__ cnt = reinterpret_cast<int*>(rec + Nn + 1);
+          int* __restrict__ cnt = reinterpret_cast<int*>(rec + rec_cnt(Nn));
           for (int q = 0; q < Nn; q++) cnt[q] = 0;
         }
-        rec[0] = S.T0[0];
-        for (int q = 0; q < S.n; q++) rec[q + 1] = xs[q];
-        if (!a.NOFLUX) rec[Nn - 1] = S.T0[Nn - 1];
-        rec[Nn] = __longlong_as_double((long long)meta);
-        a.pout[(size_t)hru * pout_hru_stride(Nn) + pout_key(Nn, ps)] = S.T0[0];
+        rec[rec_t(0)] = S.T0[0];                               // the trial temperature: the record's key
+        for (int q = 0; q < S.n; q++) rec[rec_t(q + 1)] = xs[q];
+        if (!a.NOFLUX) rec[rec_t(Nn - 1)] = S.T0[Nn - 1];
+        rec[rec_flag()] = __longlong_as_double((long long)meta);
         if (le >= 0) x.lastexp[hru] = ps;
         have = false;
       } else if (k >= ImplicitSolver::MAXTRIAL) {

@@ -261,14 +261,14 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
     PROF_ADD(11, t_stage);
     PROF_T0(t_post);
     // the soil profile of the final evaluation
-    const double* __restrict__ po = a.pout + (size_t)g * pout_hru_stride(Nn) + sv.final_slot * pout_stride(Nn);
-    const int* __restrict__ poc = reinterpret_cast<const int*>(po + Nn + 1);
+    const double* __restrict__ po = pout_rec(static_cast<const double*>(a.pout), (size_t)g, Nn, sv.final_slot);
+    const int* __restrict__ poc = reinterpret_cast<const int*>(po + rec_cnt(Nn));
     double Tprof[NN];
     int cntprof[NN];
-    const unsigned long long flags = (unsigned long long)__double_as_longlong(po[Nn]);
+    const unsigned long long flags = (unsigned long long)__double_as_longlong(po[rec_flag()]);
 #pragma unroll
     for (int n = 0; n < NN; n++) {
-      Tprof[n] = (n < Nn) ? po[n] : 0.0;
+      Tprof[n] = (n < Nn) ? po[rec_t(n)] : 0.0;
       cntprof[n] = (n < Nn) ? poc[n] : 0;
     }
     using mask_t = typename NodeBound<NN>::mask_t;      // the flag bits below the record's ok bit
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
         key = nfrozen + (kink ? NBUCKET / 2 : 0);
         a.hkey[g] = key;
       }
-      profile_item_store<NN>(o, cv, s3, w.nd, eb.delta_t, eb.frozen_on != 0, a.pin + (size_t)g * Nn * PREC);
+      profile_item_store<NN>(o, cv, s3, w.nd, eb.delta_t, eb.frozen_on != 0, item_block(a.pin, (size_t)g, Nn));
       if (o.IMPLICIT) {
         double* __restrict__ im = a.pimp + (size_t)g * Nn * PIMP;
 #pragma unroll
@@ -355,8 +355,8 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(1, 1) void vic_fd_stage(const 
         // run's own NOFLUX decides whether the bottom node is solved)
         a.jl[g] = (sv.stage == SurfSolve::ROOT_QUICK) ? tmpNnodes - 1 : (o.NOFLUX ? Nn : Nn - 1);
       }
-      a.pout[(size_t)g * pout_hru_stride(Nn) + pout_key(Nn, 0)] = NAN;      // no solve on record yet
-      a.pout[(size_t)g * pout_hru_stride(Nn) + pout_key(Nn, 1)] = NAN;
+      pout_rec(a.pout, (size_t)g, Nn, 0)[rec_key()] = NAN;      // no solve on record yet
+      pout_rec(a.pout, (size_t)g, Nn, 1)[rec_key()] = NAN;
       a.hstate[g] = 1 | (cls << HS_CLS_SHIFT);
       pend = true;
       PROF_ADD(14, t_put);
@@ -479,11 +479,11 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void v
     const Forcing fc{a.forcing, nullptr, a.ncell, c, a.o.NR + 1, a.fcol[g], a.ncol};
     surf_cell_fill(eb, cv, vl, s3, fc, eb.hidx, veg_idx, a.month);
   }
-  const double* __restrict__ rec = a.pout + (size_t)g * pout_hru_stride(a.Nn);
-  const double* __restrict__ po = rec + slot * pout_stride(a.Nn);
-  const bool ok = (((unsigned long long)__double_as_longlong(po[a.Nn])) >> record_ok_bit(node_bound(a.Nn))) & 1ull;
+  // key, flags, T1 and T2 are the record's first sector (vic_layout.hpp)
+  const double* __restrict__ po = pout_rec(static_cast<const double*>(a.pout), (size_t)g, a.Nn, slot);
+  const bool ok = (((unsigned long long)__double_as_longlong(po[rec_flag()])) >> record_ok_bit(node_bound(a.Nn))) & 1ull;
   if (sv.stage == SurfSolve::FINAL) sv.final_slot = slot;
-  const double fx = ok ? eb.eval(a.o, s3, sv.x, po[1], po[2]) : ERROR_VAL;
+  const double fx = ok ? eb.eval(a.o, s3, sv.x, po[rec_t(1)], po[rec_t(2)]) : ERROR_VAL;
   const bool was_quick = sv.stage == SurfSolve::ROOT_QUICK;
   const int stage_before = sv.stage;
   const double x_eval = sv.x;
@@ -505,16 +505,17 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(EVAL_WAVES, EVAL_WAVES) void v
     // QUICK_SOLVE: from here on the whole column is solved; the records of the shortened column are not its solutions.  NOFLUX
     // comes back with a second iteration only (calc_surf_energy_bal.c:403); the final evaluation keeps what was last set
     a.jl[g] = (sv.stage == SurfSolve::ROOT && a.o.NOFLUX) ? a.Nn : a.Nn - 1;
-    a.pout[(size_t)g * pout_hru_stride(a.Nn) + pout_key(a.Nn, 0)] = NAN;
-    a.pout[(size_t)g * pout_hru_stride(a.Nn) + pout_key(a.Nn, 1)] = NAN;
+    pout_rec(a.pout, (size_t)g, a.Nn, 0)[rec_key()] = NAN;
+    pout_rec(a.pout, (size_t)g, a.Nn, 1)[rec_key()] = NAN;
   }
   bool need_solve = sv.stage != SurfSolve::DONE;
   if (sv.stage == SurfSolve::FINAL && !a.implicit) {
     // the root has been found: the final evaluation needs the profile at sv.x, which is on record if sv.x is one of the
     // last two trial points; the evaluation itself happens in the next round, together with everybody else's (making it
     // here, in a second pass over eval(), costs the kernel 548 B of scratch per lane and 5 ms per step: measured, dropped)
-    if (rec[pout_key(a.Nn, slot)] == sv.x) { sv.final_slot = slot; sv.on_record = 1; need_solve = false; }
-    else if (rec[pout_key(a.Nn, slot ^ 1)] == sv.x) { sv.final_slot = slot ^ 1; sv.on_record = 1; need_solve = false; }
+    // (the keys are read through a.pout, as the invalidation above writes them)
+    if (pout_rec(a.pout, (size_t)g, a.Nn, slot)[rec_key()] == sv.x) { sv.final_slot = slot; sv.on_record = 1; need_solve = false; }
+    else if (pout_rec(a.pout, (size_t)g, a.Nn, slot ^ 1)[rec_key()] == sv.x) { sv.final_slot = slot ^ 1; sv.on_record = 1; need_solve = false; }
   }
   // while the Brent iteration goes on only its own state and the next abscissa change: the tail of SurfSolve (result,
   // flags, stage, record bookkeeping) is written when it does

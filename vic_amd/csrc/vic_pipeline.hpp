@@ -765,7 +765,8 @@ static int domain_fd_workspace(vicgpu_ctx* c) {
   const size_t words = NODE_DISPATCH(Nn, ctx_words);
   HIPCHK(c, d.d_ctx.alloc(ctx_padded_words(words) * ((nhru + 63) / 64 * 64)));
   HIPCHK(c, d.d_ts.alloc(nhru));
-  HIPCHK(c, d.d_pin.alloc_fill((size_t)Nn * PREC * nhru, 0, st));
+  // item blocks and solution records: sector-multiple strides on hipMalloc's (256-byte aligned) bases, vic_layout.hpp
+  HIPCHK(c, d.d_pin.alloc_fill((size_t)item_stride(Nn) * nhru, 0, st));
   HIPCHK(c, d.d_pout.alloc_fill((size_t)pout_hru_stride(Nn) * nhru, 0, st));
   HIPCHK(c, d.d_pslot.alloc_fill(nhru, 0, st));
   HIPCHK(c, d.d_hkey.alloc_fill(nhru, 0, st));

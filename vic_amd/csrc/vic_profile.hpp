@@ -66,9 +66,9 @@ VIC_DEV void list_append(int* __restrict__ list, int* count, int cap, bool pred,
 }
 
 struct PArgs {
-  const double* __restrict__ pin;    // item blocks [nhru][Nn][PREC]
+  const double* __restrict__ pin;    // item blocks [nhru][item_stride(Nn)]
   const double* __restrict__ ts;     // trial surface temperature [nhru]
-  double* __restrict__ pout;         // [nhru][pout_hru_stride(Nn)]: two solution records + the trial temperature of each
+  double* __restrict__ pout;         // [nhru][pout_hru_stride(Nn)]: two solution records
   const int* __restrict__ pslot;     // [nhru] record the next solve of this HRU is written to
   const int* __restrict__ list;      // HRUs to solve: NBUCKET segments of `cap` entries
   const int* __restrict__ count;     // entries per segment [NBUCKET]
@@ -88,14 +88,11 @@ struct PArgs {
   const int* jl;                     // QUICK_SOLVE: [nhru] nodes 1 .. jl - 1 are solved (calc_surf_energy_bal.c:289-299), or null: all
 };
 
-// One solution record: T[Nn], {fbmask | ok << NodeBound<NN>::ok_bit} (ok in bit 32 up to 24 nodes, in bit 63 above),
-// int fallback counts [Nn].  Every HRU keeps the records of its last two solves together with the trial temperatures
-// they belong to: the Brent iteration on Tsurf ends with one more evaluation AT the root, which is one of the last two
-// trial points unless the solver fell back -- the same inputs give the same profile bit for bit, so that solve is looked
-// up instead of repeated (vic_surf_eval).
-__host__ __device__ inline int pout_stride(int Nn) { return Nn + 1 + (Nn + 1) / 2; }
-__host__ __device__ inline int pout_hru_stride(int Nn) { return 2 * pout_stride(Nn) + 2; }
-__host__ __device__ inline int pout_key(int Nn, int slot) { return 2 * pout_stride(Nn) + slot; }
+// One solution record (layout and accessors: vic_layout.hpp): T[Nn], {fbmask | ok << NodeBound<NN>::ok_bit} (ok in bit 32
+// up to 24 nodes, in bit 63 above), int fallback counts [Nn].  Every HRU keeps the records of its last two solves, each
+// keyed by the trial temperature it belongs to -- T of node 0, which no sweep changes: the Brent iteration on Tsurf ends
+// with one more evaluation AT the root, which is one of the last two trial points unless the solver fell back -- the same
+// inputs give the same profile bit for bit, so that solve is looked up instead of repeated (vic_surf_eval).
 
 constexpr int LOCKSTEP_GATE = 16;   // idle lanes that must be waiting before the write-back / fetch section runs
 
@@ -407,17 +404,17 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
       const int slot = base + __popcll(idle & ((1ull << lane) - 1ull));
       if (!have && slot < n) {
         hru = profile_pick(a, bcount, slot);
-        // an item block starts on a 16-byte boundary (10 nodes x 11 doubles = 880 bytes): lets pairs of words load as one access
-        const double* __restrict__ blk = static_cast<const double*>(__builtin_assume_aligned(a.pin + (size_t)hru * Nn * PREC, 16));
+        // header, start column and interior records: one contiguous run of the block (item_block: pairs of words load as one access)
+        const double* __restrict__ blk = item_block(a.pin, (size_t)hru, Nn);
         ps = a.pslot[hru];
         jl_lane = a.jl ? a.jl[hru] : jlast;
-        frozen_on = blk[PR_AT0] != 0.0;
+        frozen_on = blk[item_header()] != 0.0;
         const double Ts = a.ts[hru];
 #pragma unroll
-        for (int k = 0; k < NN; k++) { const double t = (k == 0) ? Ts : blk[k * PREC + PR_T0]; T0(k) = t; T[k] = t; }
+        for (int k = 0; k < NN; k++) { const double t = (k == 0) ? Ts : blk[item_t0(k)]; T0(k) = t; T[k] = t; }
 #pragma unroll
         for (int k = 1; k < NN - 1; k++) {
-          const double* __restrict__ r = blk + k * PREC;
+          const double* __restrict__ r = blk + item_rec(Nn, k);
           kAT0[k] = r[PR_AT0]; kB[k] = r[PR_B]; kC[k] = r[PR_C]; kD[k] = r[PR_D]; kEI[k] = r[PR_EI]; kS[k] = r[PR_S]; kEMM[k] = r[PR_EMM];
           KL(0, k) = r[PR_G]; KL(1, k) = r[PR_Y]; KL(2, k) = r[PR_EMOIST];
         }
@@ -439,7 +436,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
           const double Tdn = (j == Nn - 1) ? oldT : T[(j + 1 < NN) ? j + 1 : j], Tup = T[j - 1];
           const double T0j = T0(j);
           NodeK Kj;
-          if (j == NN - 1) Kj.load(a.pin + ((size_t)hru * Nn + j) * PREC);      // the bottom node (NOFLUX only) is not cached
+          if (j == NN - 1) Kj.load(item_block(a.pin, (size_t)hru, Nn) + item_rec(Nn, j));      // the bottom node (NOFLUX only) is not cached
           else {
             constexpr int q = 0;
             const int jj = (j < NN - 1) ? j : 1 + q;
@@ -456,7 +453,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
               if (a.TFALLBACK) {
                 // node fallback: T0 and a count.  The counters live in the solution record (rare path): the first event of a
                 // solve clears them, the end of the solve adds its own events or, without any, writes them whole
-                int* cnt = reinterpret_cast<int*>(a.pout + (size_t)hru * pout_hru_stride(Nn) + ps * pout_stride(Nn) + Nn + 1);
+                int* cnt = reinterpret_cast<int*>(pout_rec(a.pout, (size_t)hru, Nn, ps) + rec_cnt(Nn));
                 if (evcnt == 0) {
 #pragma unroll
                   for (int k = 0; k < NN; k++) cnt[k] = 0;
@@ -488,18 +485,19 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
 #pragma unroll
       for (int k = 0; k < NN; k++) T0v[k] = T0(k);
       profile_finish<NN>(a.jl ? (jl_lane + 1 < Nn ? jl_lane + 1 : Nn) : Nn, a.TFALLBACK != 0, converged, ok, fbmask, T, T0v, cadd);
-      double* __restrict__ rec = a.pout + (size_t)hru * pout_hru_stride(Nn) + ps * pout_stride(Nn);
-      int* __restrict__ cnt = reinterpret_cast<int*>(rec + Nn + 1);
+      // the whole record: at 10 nodes two full sectors.  T[0] is still the trial temperature (sweeps start at node 1, the
+      // fall-backs restore T0): the record's key
+      double* __restrict__ rec = pout_rec(a.pout, (size_t)hru, Nn, ps);
+      int* __restrict__ cnt = reinterpret_cast<int*>(rec + rec_cnt(Nn));
 #pragma unroll
-      for (int k = 0; k < NN; k++) rec[k] = T[k];
-      rec[Nn] = __longlong_as_double((long long)((unsigned long long)fbmask | ((unsigned long long)(ok ? 1 : 0) << 32)));
+      for (int k = 0; k < NN; k++) rec[rec_t(k)] = T[k];
+      rec[rec_flag()] = __longlong_as_double((long long)((unsigned long long)fbmask | ((unsigned long long)(ok ? 1 : 0) << 32)));
       // fallback counters: zero unless something happened in this solve (node-solver fallbacks were written as they happened)
 #pragma unroll
       for (int k = 0; k < NN; k++) {
         if (evcnt == 0) cnt[k] = cadd[k];
         else cnt[k] += cadd[k];
       }
-      a.pout[(size_t)hru * pout_hru_stride(Nn) + pout_key(Nn, ps)] = T0(0);
       have = false;
     }
     PROF_ADD(24, t_fin);
@@ -511,8 +509,8 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(PROFILE_REG_WAVES, PROFILE_REG
 // ------------------------------------------------------------------------------------------------
 // any node count: node columns in LDS, the node's record read at each visit.  The start column T0 is in LDS up to
 // VIC_MID_NODES nodes; the deep bound (up to 50 nodes, where both columns would take 51 KB of LDS per wave) takes T0 of
-// node j >= 1 from the node's record, which the visit reads anyway, and T0 of node 0 (the trial surface temperature)
-// from a register: 25.6 KB per wave
+// node j >= 1 from the item block's start column and T0 of node 0 (the trial surface temperature) from a register:
+// 25.6 KB per wave
 // ------------------------------------------------------------------------------------------------
 constexpr int LS_WAVES = 2;
 template <int NN, bool NEWTON>
@@ -524,7 +522,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
   __shared__ double T0l[T0_LDS ? NN * 64 : 1];
   const int lane = threadIdx.x;
 #define T(j) Tl[(j) * 64 + lane]
-#define T0(j) (T0_LDS ? T0l[(T0_LDS ? (j) : 0) * 64 + lane] : ((j) == 0 ? T0s : blk[(j) * PREC + PR_T0]))
+#define T0(j) (T0_LDS ? T0l[(T0_LDS ? (j) : 0) * 64 + lane] : ((j) == 0 ? T0s : blk[item_t0(j)]))
   for (int b = lane; b < NBUCKET; b += 64) bcount[b] = a.count[b];
   if (blockIdx.x == 0) {
     for (int b = lane; b < NBUCKET; b += 64) a.count_zero[b] = 0;
@@ -545,8 +543,8 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
   const double threshold = 1.e-2;
   const bool EXP_TRANS = a.EXP_TRANS != 0;
 
-#define LS_REC() (a.pout + (size_t)hru * pout_hru_stride(Nn) + ps * pout_stride(Nn))
-#define LS_CNT(j) (reinterpret_cast<int*>(LS_REC() + Nn + 1)[j])
+#define LS_REC() pout_rec(a.pout, (size_t)hru, Nn, ps)
+#define LS_CNT(j) (reinterpret_cast<int*>(LS_REC() + rec_cnt(Nn))[j])
   bool have = false, sweeping = false, converged = false, ok = true, frozen_on = false;
   int hru = 0, ps = 0, it = 1, jl_lane = 0;
   mask_t fbmask = 0;
@@ -564,15 +562,15 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
       const int slot = base + __popcll(idle & ((1ull << lane) - 1ull));
       if (!have && slot < n) {
         hru = profile_pick(a, bcount, slot);
-        blk = a.pin + (size_t)hru * Nn * PREC;
+        blk = item_block(a.pin, (size_t)hru, Nn);
         ps = a.pslot[hru];
         jl_lane = a.jl ? a.jl[hru] : jlast;
-        frozen_on = blk[PR_AT0] != 0.0;
+        frozen_on = blk[item_header()] != 0.0;
         const double Ts = a.ts[hru];
 #pragma unroll
         for (int k = 0; k < NN; k++)
           if (k < Nn) {
-            const double t = (k == 0) ? Ts : blk[k * PREC + PR_T0];
+            const double t = (k == 0) ? Ts : blk[item_t0(k)];
             if constexpr (T0_LDS) T0l[k * 64 + lane] = t;
             T(k) = t; LS_CNT(k) = 0;
           }
@@ -596,7 +594,7 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
             oldT = T(j);
             Tdn = (j == Nn - 1) ? oldT : T((j + 1 < NN) ? j + 1 : j); Tup = T(j - 1);
             T0j = T0(j);
-            K.load(blk + j * PREC);
+            K.load(blk + item_rec(Nn, j));
           }
           bool failed;
           double newT;
@@ -644,9 +642,8 @@ __global__ __launch_bounds__(64) VIC_WAVES_PER_EU(LS_WAVES, LS_WAVES) void vic_p
       }
       double* __restrict__ rec = LS_REC();
 #pragma unroll 1
-      for (int k = 0; k < Nn; k++) rec[k] = T(k);
-      rec[Nn] = profile_flag_word<NN>(fbmask, ok);
-      a.pout[(size_t)hru * pout_hru_stride(Nn) + pout_key(Nn, ps)] = T0(0);
+      for (int k = 0; k < Nn; k++) rec[rec_t(k)] = T(k);      // T(0) is the trial temperature: the record's key
+      rec[rec_flag()] = profile_flag_word<NN>(fbmask, ok);
       have = false;
     }
   }

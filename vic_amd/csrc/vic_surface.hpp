@@ -1,6 +1,7 @@
 // vic_surface.hpp — ground-surface energy balance, soil temperature profile, solve_snow (device only, gfx950).
 #pragma once
 #include "vic_snow.hpp"
+#include "vic_layout.hpp"
 
 namespace vic {
 
@@ -16,7 +17,8 @@ VIC_DEV double estimate_T1(double Ts, double T1_old, double T2, double D1, doubl
 
 // ------------------------------------------------------------------------------------------------
 // Finite-difference soil temperature profile: what the ground-surface balance hands to the profile-solve kernel
-// (vic_profile.hpp).  One record per node, PREC doubles, records of one HRU contiguous ("item block").
+// (vic_profile.hpp).  Per HRU one "item block": a header word, the start column T0 and one record of PREC doubles per node
+// below the surface (layout and accessors: vic_layout.hpp).
 //
 // The explicit scheme (frozen_soil.c:161-213, 380-468) updates node j from its neighbours TL = T[j+1], TU = T[j-1]:
 //   unfrozen node:  T = N / S                                  with N = A*T0 + B*(TL-TU) + C*TL + D*TU + E*(0-ice0), S = A+C+D
@@ -24,23 +26,23 @@ VIC_DEV double estimate_T1(double Ts, double T1_old, double T2, double D1, doubl
 //                   which is, term by term,  N - S*T + E*ice(T)   with the SAME N and S,
 //   ice(T) = clip(moist - u(T)), u(T) = max_moist * (-Lf*T/273.16/(g*bubble/100))^(-2/(expt-3)) clipped to max_moist
 //   (maximum_unfrozen_water, soil_conduction.c:830-863); EXP_TRANS: N and S of frozen_soil.c:194-212 instead.
-// So a record holds what both forms need, with everything that is constant over the Brent solve on Tsurf folded once
+// So a block holds what both forms need, with everything that is constant over the Brent solve on Tsurf folded once
 // per sub-step here instead of once per node visit there:
-//   [0] T0     previous-step temperature (node 0: replaced by the trial surface temperature at solve time)
-//   [1] A*T0   (node 0: frozen_on flag)
-//   [2] B  [3] C  [4] D  [5] E*(0-ice0)  [6] S = A+C+D  (EXP_TRANS: A+2C)        -> N and the closed-form update keep the
+//   header     frozen_on flag
+//   T0 column  previous-step temperature of every node (node 0: replaced by the trial surface temperature at solve time)
+//   per node 1 .. Nn-1 (the bottom node with NOFLUX only):
+//   [0] A*T0
+//   [1] B  [2] C  [3] D  [4] E*(0-ice0)  [5] S = A+C+D  (EXP_TRANS: A+2C)        -> N and the closed-form update keep the
 //                                                                                  reference's operation order exactly
-//   [7] G = E*max_moist*kappa^Y, kappa = Lf/273.16/(g*bubble/100)   [8] Y = -2/(expt-3)       -> E*u(T) = G*(-T)^Y
-//   [9] E*moist  [10] E*max_moist                                                               (clip levels of E*u, E*ice)
+//   [6] G = E*max_moist*kappa^Y, kappa = Lf/273.16/(g*bubble/100)   [7] Y = -2/(expt-3)       -> E*u(T) = G*(-T)^Y
+//   [8] E*moist  [9] E*max_moist                                                                (clip levels of E*u, E*ice)
 // max_moist/bubble/expt are the node arrays ("fixed") or the LAYER arrays indexed by node as shipped ("compat",
 // frozen_soil.c:218-221: max_moist in mm for j < 3, then the node arrays shifted by 3).
 // A-D depend only on kappa, Cs, the node geometry and dt, i.e. they are the same for every residual evaluation of one
 // Brent solve on Tsurf (upstream keeps them in static arrays for that reason; SURVEY.md Finding 1.1).
 // ------------------------------------------------------------------------------------------------
-constexpr int PREC = 11;
-enum { PR_T0 = 0, PR_AT0, PR_B, PR_C, PR_D, PR_EI, PR_S, PR_G, PR_Y, PR_EMOIST, PR_EMM };
 
-// The per-node part of a record (everything but T0): the reference's coefficients A-E of the node and its freezing parameters
+// A node's record: the reference's coefficients A-E of the node and its freezing parameters
 // (max_moist mm, bubble, expt) folded as listed above.  Shared by profile_item_store and the node-root test hook
 // (vicgpu_debug_node_root), so that the hook tests the record the pipeline builds.
 VIC_DEV void profile_node_fold(double* r, bool EXP_TRANS, bool frozen_on, double A, double B, double C, double D, double E,
@@ -64,13 +66,17 @@ VIC_DEV void profile_item_store(const Opt& o, const CellView& cv, const Soil3& s
   const int Nn = node_count<NN>(o.Nnode);
   const double Dp = cv.s(CP_DP);
   const double Bexp = o.EXP_TRANS ? log(Dp + 1.) / (double)(Nn - 1) : 0.0;
+  // header and start column in one go: their two sectors fill back to back, not one word per node between the records' folds
+  // ("Round tables")
+  blk[item_header()] = frozen_on ? 1.0 : 0.0;
 #pragma unroll
-  for (int j = 0; j < NN; j++) {
+  for (int j = 0; j < NN; j++)
+    if (j < Nn) blk[item_t0(j)] = nd.T[j];
+#pragma unroll
+  for (int j = 1; j < NN; j++) {
     if (j >= Nn) continue;
-    double* r = blk + j * PREC;
-    r[PR_T0] = nd.T[j];
-    if (j == 0) { r[PR_AT0] = frozen_on ? 1.0 : 0.0; continue; }
     if (!(j < Nn - 1 || o.NOFLUX)) continue;
+    double* r = blk + item_rec(Nn, j);
     const double kup = (j < Nn - 1) ? nd.kappa[(j + 1 < NN) ? j + 1 : j] : nd.kappa[j];
     double A, C, D, E;
     if (!o.EXP_TRANS) {
