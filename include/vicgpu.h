@@ -679,6 +679,56 @@ int vicgpu_mix_cells(vicgpu_ctx *ctx, int nrow, const int *rows,
                      const int *term_cell,       /* [nnz], each in [0, ncell) */
                      const double *term_weight); /* [nnz], finite */
 
+/* ---- the per-column ensemble transform solved and applied on the device: the analysis of a localised filter (LETKF, Hunt et
+ * al. 2007), one transform per base column, without an eigendecomposition on the host and without term lists.
+ * Layout: the ensemble is member-major (domain.tile_members): ncell == nmember * ncol, and cell m * ncol + j is member m of base
+ * column j.  T[j][m'][m] is the weight of forecast member m' in analysis member m of column j.
+ * Lifetime: the context holds one stored transform, in device memory.  solve and set replace it, vicgpu_set_domain and
+ * vicgpu_destroy drop it, get and apply without one return VICGPU_ERR_STATE.
+ *   vicgpu_member_transform_solve   computes T_j for every column from the members' observation-space values.  For column j
+ *       with the observations p in [obs_off[j], obs_off[j + 1]), M = nmember and rho = infl[j]:
+ *         ybar_p = (sum over m of hx[p][m]) / M,  Y_p[m] = hx[p][m] - ybar_p,  d_p = yobs[p] - ybar_p,
+ *         C[a][b] = sum over p of (rinv_p * Y_p[a]) * Y_p[b],  g[a] = sum over p of (rinv_p * Y_p[a]) * d_p,
+ *         A = C + ((M - 1) / rho) I = U diag(lam) U^T,  wbar = U diag(1 / lam) U^T g,  Wa = U diag(sqrt((M - 1) / lam)) U^T,
+ *         W[m'][m] = Wa[m'][m] + wbar[m'],  T[m'][m] = W[m'][m] + (1 - sum over m'' of W[m''][m]) / M.
+ *       The last term folds "about the ensemble mean" into a pure member mix: x_a[m] = sum over m' of T[m'][m] * x_f[m'] is the
+ *       LETKF analysis, and every column of T sums to 1.  The eigen-solver is a batched parallel cyclic Jacobi iteration, one
+ *       wave per column.  Guaranteed: (a) the result is bit-identical from run to run; (b) T_j does not depend on which other
+ *       columns are in the call; (c) a column with no observation, or with every rinv == 0, performs no rotation and gives
+ *       exactly sqrt(rho) * I + (1 - sqrt(rho)) / M -- with rho == 1 the exact identity, which leaves finite state
+ *       bit-identical (but for a -0.0, which the zero terms of the sum turn into +0.0); (d) a column that has not converged after VICGPU_TRANSFORM_SWEEPS sweeps (a tuning variable, default
+ *       30) gets the exact identity and info[j] = -1, and the call still returns VICGPU_OK.  Beyond these the bits of T are
+ *       not part of the contract; its accuracy is (that of a float64 LAPACK evaluation of the formulas).  info[j] otherwise
+ *       counts the sweeps that rotated.  The solve touches no model table.
+ *   vicgpu_member_transform_set     stores the caller's T.
+ *   vicgpu_member_transform_get     the sizes and, unless T is NULL, the stored transform.
+ *   vicgpu_member_transform_apply   applies the stored transform to the listed rows of the SD table for the listed base columns
+ *       (cols NULL: all, n must be ncol).  The members of a listed column must satisfy the pair rule of vicgpu_copy_cells.
+ *       Arithmetic (part of the contract): vicgpu_mix_cells' own.  For destination member m, column j, HRU position k and a
+ *       listed row, p = T[j][0][m] * x_0, then p = p + T[j][m'][m] * x_m' for m' = 1 .. M - 1, every product and every sum
+ *       rounded once; a zero weight still reads its operand; all sources are read before any destination is written.  The call
+ *       equals vicgpu_mix_cells with the lists of domain.member_transform(M, ncol, T, cols) bit for bit, NaNs by position.
+ *       Untouched tables, stream order and staging (row passes within VICGPU_COPY_STAGE_MB, the result independent of the
+ *       budget) are vicgpu_mix_cells' as well.  nrow == 0 and n == 0 are legal and change nothing.
+ * Every list is checked, and everything is allocated, before the first write; a failing call leaves every table and the stored
+ * transform bit-identical.
+ * VICGPU_ERR_ARG: a null handle; nmember outside [2, VICGPU_TRANSFORM_MAX_MEMBERS]; ncol < 1 or nmember * ncol != ncell; null
+ * lists with work to do; obs_off[0] != 0 or decreasing offsets; a non-finite hx, yobs, rinv, infl or T; rinv < 0 or infl <= 0;
+ * a row out of range or listed twice; a column out of range or listed twice; members of a listed column that break the pair
+ * rule (vicgpu_last_error names the column and the member); VICGPU_ERR_STATE: no domain; get or apply without a stored
+ * transform; VICGPU_ERR_HIP: the runtime refused an allocation -- nothing is left behind. */
+#define VICGPU_TRANSFORM_MAX_MEMBERS 64
+int vicgpu_member_transform_solve(vicgpu_ctx *ctx, int nmember, int ncol,
+        const int *obs_off,     /* [ncol+1], obs_off[0] = 0, non-decreasing; nobs = obs_off[ncol] */
+        const double *hx,       /* [nobs][nmember]  H x of every member, finite */
+        const double *yobs,     /* [nobs]           the observation, finite */
+        const double *rinv,     /* [nobs]           1 / error variance times the localisation taper; finite, >= 0 */
+        const double *infl,     /* [ncol] or NULL (= 1.0): multiplicative covariance inflation rho_j, finite, > 0 */
+        int *info);             /* [ncol] or NULL: sweeps the column took (>= 0), or -1: not converged */
+int vicgpu_member_transform_set(vicgpu_ctx *ctx, int nmember, int ncol, const double *T); /* [ncol][nmember][nmember], finite */
+int vicgpu_member_transform_get(vicgpu_ctx *ctx, int *nmember, int *ncol, double *T);     /* T may be NULL: sizes only */
+int vicgpu_member_transform_apply(vicgpu_ctx *ctx, int nrow, const int *rows, int n, const int *cols); /* cols NULL: all, n must be ncol */
+
 /* ---- plumbing for callers that own device memory / streams --------------- */
 int   vicgpu_set_stream(vicgpu_ctx *ctx, void *hip_stream);       /* compute stream; NULL = library-owned */
 int   vicgpu_set_write_fluxes(vicgpu_ctx *ctx, int on);           /* 0: skip the per-HRU flux table (accumulators still kept) */

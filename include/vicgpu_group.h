@@ -121,7 +121,9 @@ int vicgpu_group_update_state_i(vicgpu_group *g, int nrow, const int *rows, int 
 int vicgpu_group_derive_soil_state(vicgpu_group *g, int n, const int *hrus, int what);
 /* vicgpu_mix_cells (vicgpu.h) has no group form: under the group's contiguous sharding the members of a member-major ensemble
  * lie on different devices, so a transform would be an all-to-all between shards with a summation order of its own, which is a
- * decision of its own.  A shard's context (vicgpu_group_shard_ctx) takes vicgpu_mix_cells in its local numbering. */
+ * decision of its own.  A shard's context (vicgpu_group_shard_ctx) takes vicgpu_mix_cells in its local numbering.
+ * vicgpu_member_transform_solve, vicgpu_member_transform_set, vicgpu_member_transform_get and vicgpu_member_transform_apply
+ * (vicgpu.h) have no group form for the same reason: a column's members would lie on different devices. */
 int vicgpu_group_get_state_records(vicgpu_group *g, double *records);
 int vicgpu_group_set_state_records(vicgpu_group *g, const double *records);   /* checks every record before any shard scatters */
 int vicgpu_group_glacier_mass_balance_fit(vicgpu_group *g, double *eq, int reset);

@@ -87,6 +87,10 @@ def load_library():
         "vicgpu_update_state_i": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip]),
         "vicgpu_derive_soil_state": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int]),
         "vicgpu_mix_cells": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip, _ip, _ip, _dp]),
+        "vicgpu_member_transform_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _ip, _dp, _dp, _dp, _dp, _ip]),
+        "vicgpu_member_transform_set": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, _dp]),
+        "vicgpu_member_transform_get": (ctypes.c_int, [vp, _ip, _ip, _dp]),
+        "vicgpu_member_transform_apply": (ctypes.c_int, [vp, ctypes.c_int, _ip, ctypes.c_int, _ip]),
         "vicgpu_host_alloc": (vp, [ctypes.c_size_t]),
         "vicgpu_host_free": (None, [vp]),
         "vicgpu_get_state_records": (ctypes.c_int, [vp, _dp]),
@@ -197,7 +201,8 @@ EXPORTED_SYMBOLS = [
     "vicgpu_update_cell_params", "vicgpu_update_hru_params", "vicgpu_get_cell_params", "vicgpu_get_hru_params",
     "vicgpu_get_state_rows", "vicgpu_get_state_rows_i", "vicgpu_update_state", "vicgpu_update_state_i", "vicgpu_derive_soil_state",
     "vicgpu_mix_cells",
-] + ["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
+    "vicgpu_member_transform_solve", "vicgpu_member_transform_set", "vicgpu_member_transform_get", "vicgpu_member_transform_apply",
+] +["vicgpu_group_" + n for n in GROUP_ENTRIES + ["partition", "create", "shard_bounds", "shard_ctx"]]
 
 
 def _d(a):
@@ -487,6 +492,55 @@ class Model:
         assert len(c) == o[-1], (len(c), int(o[-1]))
         self._chk(self.lib.vicgpu_mix_cells(self.h, len(r), _i(r), len(d), _i(d), _i(o), _i(c), _d(w)))
 
+    # ---- the per-column ensemble transform of a localised filter, solved and applied on the device
+    def member_transform_solve(self, nmember, obs_off, hx, yobs, rinv, infl=None):
+        """vicgpu_member_transform_solve: the LETKF transform of every base column of the member-major ensemble (cell
+        m * ncol + j is member m of column j) from hx [nobs][nmember], yobs [nobs] and rinv [nobs], column j owning the
+        observations obs_off[j] .. obs_off[j + 1] - 1; infl [ncol] is the covariance inflation (default 1).  The transform stays
+        on the device (member_transform_get reads it).  Returns info [ncol]: the sweeps a column took, or -1 where it did not
+        converge and got the identity."""
+        M = int(nmember)
+        o = np.ascontiguousarray(obs_off, dtype=np.int32)
+        assert o.ndim == 1 and len(o) >= 2, o.shape
+        ncol, nobs = len(o) - 1, int(o[-1])
+        h = np.ascontiguousarray(hx, dtype=np.float64)
+        y = np.ascontiguousarray(yobs, dtype=np.float64)
+        r = np.ascontiguousarray(rinv, dtype=np.float64)
+        assert h.shape == (nobs, M) and y.shape == (nobs,) and r.shape == (nobs,), (h.shape, y.shape, r.shape, nobs, M)
+        f = None if infl is None else np.ascontiguousarray(infl, dtype=np.float64)
+        assert f is None or f.shape == (ncol,), f.shape
+        info = np.zeros(ncol, dtype=np.int32)
+        self._chk(self.lib.vicgpu_member_transform_solve(self.h, M, ncol, _i(o), _d(h), _d(y), _d(r), None if f is None else _d(f), _i(info)))
+        return info
+
+    def member_transform_set(self, T):
+        """vicgpu_member_transform_set: stores T [ncol][nmember][nmember], T[j, m', m] as domain.member_transform's 3-D W."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        assert T.ndim == 3 and T.shape[1] == T.shape[2], T.shape
+        self._chk(self.lib.vicgpu_member_transform_set(self.h, T.shape[1], T.shape[0], _d(T)))
+
+    def member_transform_get(self):
+        """vicgpu_member_transform_get: the stored transform, [ncol][nmember][nmember]."""
+        M, n = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.vicgpu_member_transform_get(self.h, ctypes.byref(M), ctypes.byref(n), None))
+        T = np.zeros((n.value, M.value, M.value))
+        self._chk(self.lib.vicgpu_member_transform_get(self.h, ctypes.byref(M), ctypes.byref(n), _d(T)))
+        return T
+
+    def member_transform_apply(self, rows, cols=None):
+        """vicgpu_member_transform_apply: the stored transform on the SD rows `rows` of the base columns `cols` (default: all);
+        bit for bit mix_cells(rows, *domain.member_transform(M, ncol, T, cols)).  No other row follows: derive_soil_state."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        assert r.ndim == 1, r.shape
+        if cols is None:
+            M, n = ctypes.c_int(0), ctypes.c_int(0)
+            self._chk(self.lib.vicgpu_member_transform_get(self.h, ctypes.byref(M), ctypes.byref(n), None))
+            self._chk(self.lib.vicgpu_member_transform_apply(self.h, len(r), _i(r), n.value, None))
+        else:
+            c = np.ascontiguousarray(cols, dtype=np.int32)
+            assert c.ndim == 1, c.shape
+            self._chk(self.lib.vicgpu_member_transform_apply(self.h, len(r), _i(r), len(c), _i(c)))
+
     def get_forcing(self, step):
         f = np.zeros((C["VIC_NFORCE"], self.opt.NR + 1, self.ncol)); sf = np.zeros((self.opt.NR + 1, self.dom.ncell), dtype=np.uint8)
         self._chk(self.lib.vicgpu_get_forcing(self.h, int(step), _d(f), sf.ctypes.data_as(_up)))
@@ -764,6 +818,11 @@ class Group(Model):
     # ---- a mix across shards would be an all-to-all with a summation order of its own (include/vicgpu_group.h)
     def mix_cells(self, rows, dst_cells, term_off, term_cell, term_weight):
         raise VicGpuError("mix_cells has no device-group form: give a shard's context (shard_ctx) the call in its local numbering")
+
+    def _no_member_transform(self, *args, **kw):
+        raise VicGpuError("the member transform has no device-group form: a column's members would lie on different devices")
+
+    member_transform_solve = member_transform_set = member_transform_get = member_transform_apply = _no_member_transform
 
     def shard_ctx(self, k):
         """Shard k's vicgpu_ctx handle, for the per-context entries (stream, tuning, debug)."""

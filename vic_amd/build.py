@@ -57,6 +57,10 @@ RESOURCE_LIMITS = {
     "vic_cell_reduce": (128, 0),
     # a small streaming kernel that lives on waves in flight: at least four per SIMD, accumulators in registers
     "vic::vic_mix_cells": (128, 0),
+    # the member transform (vic_member_transform.hpp): the batched Jacobi solver keeps its matrices in LDS and a handful of
+    # scalars per lane; the apply is vic_mix_cells with an implied term walk and lives on waves in flight like it
+    "vic::vic_member_transform_solve": (128, 0),
+    "vic::vic_member_transform_apply": (128, 0),
     # the row gather and scatter (vic_rows.hpp): eight values in flight per lane and nothing else, full occupancy, no scratch;
     # a ceiling a little above today's 22 VGPRs
     "vic::vic_rows_": (32, 0),

@@ -29,6 +29,7 @@
 #include "vic_params.hpp"
 #include "vic_state_update.hpp"
 #include "vic_mix_cells.hpp"
+#include "vic_member_transform.hpp"
 
 using namespace vic;
 
@@ -93,6 +94,10 @@ struct Domain {
   std::vector<int> cell_off, cell_list, copy_key;
   std::vector<int> cell_class;     // [ncell] copy_cell_classes of them, built by the first vicgpu_mix_cells of the domain
   MixPlan mix_plan;                // ... and the plan of its last one, whose memory the next one reuses
+  // the stored member transform (vicgpu_member_transform_solve / _set): [tf_ncol][tf_nmember][tf_nmember], empty when there is none
+  int tf_nmember = 0, tf_ncol = 0;
+  DevBuf<double> d_transform;
+  TransformPlan transform_plan;    // the plan of the last vicgpu_member_transform_apply, reused like mix_plan
   // finite-difference pipeline workspace (allocated when QUICK_FLUX is off)
   bool fd = false;
   DevBuf<unsigned long long> d_ctx;
@@ -125,6 +130,7 @@ struct Tuning {
   bool trace = false;              // VICGPU_TRACE (set): per-step wall time and Brent rounds (a wait per step)
   bool stats = false;              // VICGPU_STATS (set): Brent rounds per step of every chunk, printed by vicgpu_destroy; the record groups' reduce time
   int copy_stage_mb = 256;         // VICGPU_COPY_STAGE_MB, 0..65536: staging memory of a vicgpu_copy_cells call on the staged path; 0 = one row per pass
+  int transform_sweeps = 30;       // VICGPU_TRANSFORM_SWEEPS, 1..1000: Jacobi sweeps a column of vicgpu_member_transform_solve may take
 };
 static Tuning read_tuning(int node_solver, int ncell) {
   Tuning t;
@@ -159,6 +165,11 @@ static Tuning read_tuning(int node_solver, int ncell) {
   if (const char* ev = getenv("VICGPU_COPY_STAGE_MB")) {
     const int mb = atoi(ev);
     if (mb >= 0 && mb <= 65536) t.copy_stage_mb = mb;
+  }
+  // vicgpu_member_transform_solve: a column still rotating after this many sweeps gets the identity
+  if (const char* ev = getenv("VICGPU_TRANSFORM_SWEEPS")) {
+    const int n = atoi(ev);
+    if (n >= 1 && n <= 1000) t.transform_sweeps = n;
   }
   return t;
 }

@@ -1,6 +1,6 @@
 // vic_rows.hpp — listed rows and columns of a [row][column] device table moved through a budgeted stage: what
-// vicgpu_copy_cells, vicgpu_update_cell_params / _hru_params, vicgpu_get_state_rows / _update_state and vicgpu_mix_cells
-// (include/vicgpu.h) and their device-group forms have in common.  The check of a call's lists on the host, the gather and the
+// vicgpu_copy_cells, vicgpu_update_cell_params / _hru_params, vicgpu_get_state_rows / _update_state, vicgpu_mix_cells and
+// vicgpu_member_transform_apply (include/vicgpu.h) and their device-group forms have in common.  The check of a call's lists on the host, the gather and the
 // scatter kernel for gfx950, their launchers and the pass loop.  Nothing here knows a context: a table is a [..][ld] array of
 // double or int, the lists are row and column indices.
 //

@@ -17,6 +17,8 @@
 //   vic_state_update.hpp vicgpu_get_state_rows / _update_state / _derive_soil_state: vic_derive_soil_state, the tail of
 //                        initialize_model_state for listed HRUs
 //   vic_mix_cells.hpp    vicgpu_mix_cells: the host planning of a linear combination across cells and vic_mix_cells
+//   vic_member_transform.hpp  vicgpu_member_transform_solve / _set / _get / _apply: the checks of a call, the batched Jacobi
+//                        eigen-solver vic_member_transform_solve and vic_member_transform_apply, vic_mix_cells with implied terms
 //   vic_host.hpp         owners of every device buffer, pinned block, stream and event; the buffers' counted transfers; the
 //                        VICGPU_STATS timer of an entry
 //   vic_checks.hpp       the domain-list and state-record checks (no HIP), shared with the group
@@ -53,6 +55,7 @@
 #include "vic_params.hpp"
 #include "vic_state_update.hpp"
 #include "vic_mix_cells.hpp"
+#include "vic_member_transform.hpp"
 #include "vic_pipeline.hpp"
 #include "vic_group.hpp"
 
@@ -1181,6 +1184,151 @@ int vicgpu_mix_cells(vicgpu_ctx* c, int nrow, const int* rows, int ndst, const i
   if (timer.elapsed(&ms))
     fprintf(stderr, "[vicgpu] mix_cells: %d destinations, %d HRUs, %d terms, %d rows, %d passes, %zu bytes written: %.4f ms on the device\n", ndst, n,
             nnz, nrow, (nrow + rpp - 1) / rpp, sizeof(double) * nrow * n, ms);
+  return VICGPU_OK;
+}
+
+// ---- the per-column ensemble transform solved and applied on the device (vic_member_transform.hpp): the analysis of a localised
+// filter.  The domain holds the stored transform; a call that fails leaves it as it was: solve and set fill a fresh buffer and
+// the domain takes it at the end.
+static int transform_sizes_check(vicgpu_ctx* c, int nmember, int ncol) {
+  if (!c || nmember < 2 || nmember > VICGPU_TRANSFORM_MAX_MEMBERS || ncol < 1) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready) return VICGPU_ERR_STATE;
+  if ((long long)nmember * ncol != (long long)c->dom.ncell) return VICGPU_ERR_ARG;
+  return VICGPU_OK;
+}
+
+int vicgpu_member_transform_solve(vicgpu_ctx* c, int nmember, int ncol, const int* obs_off, const double* hx, const double* yobs,
+                                  const double* rinv, const double* infl, int* info) {
+  const int r = transform_sizes_check(c, nmember, ncol);
+  if (r != VICGPU_OK) return r;
+  if (!obs_off) return VICGPU_ERR_ARG;
+  if (obs_off[0] != 0) { c->err = "member_transform_solve: obs_off does not start at 0"; return VICGPU_ERR_ARG; }
+  for (int j = 0; j < ncol; j++)
+    if (obs_off[j + 1] < obs_off[j]) { c->err = "member_transform_solve: column " + std::to_string(j) + ": obs_off decreases"; return VICGPU_ERR_ARG; }
+  const int nobs = obs_off[ncol];
+  if (nobs > 0 && (!hx || !yobs || !rinv)) return VICGPU_ERR_ARG;
+  // every list is checked here, before anything is queued
+  const SolveFault f = check_transform_solve(nmember, ncol, obs_off, hx, yobs, rinv, infl);
+  if (f.rule != MT_OK) { c->err = solve_fault_text(f); return VICGPU_ERR_ARG; }
+  Domain& d = c->dom;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t M = (size_t)nmember, un = (size_t)ncol, uo = (size_t)nobs, no1 = uo ? uo : 1;
+  // what the call allocates, before anything is queued: [obs_off][info], [hx][yobs][rinv][infl][sqrt(infl)], the new transform
+  DevBuf<int> ints;
+  DevBuf<double> obs, fresh;
+  HIPCHK(c, ints.alloc(2 * un + 1));
+  HIPCHK(c, obs.alloc(no1 * (M + 2) + 2 * un));
+  HIPCHK(c, fresh.alloc(un * M * M));
+  const size_t at_y = no1 * M, at_r = at_y + no1, at_infl = at_r + no1, at_sq = at_infl + un;
+  StreamTimer timer;               // tuning (VICGPU_STATS): the kernel's own time
+  HIPCHK(c, timer.create(c->tune.stats));
+  HIPCHK(c, ints.upload(c->stream, obs_off, 0, un + 1));
+  if (nobs > 0) {
+    HIPCHK(c, obs.upload(c->stream, hx, 0, uo * M));
+    HIPCHK(c, obs.upload(c->stream, yobs, at_y, uo));
+    HIPCHK(c, obs.upload(c->stream, rinv, at_r, uo));
+  }
+  if (infl) {
+    std::vector<double> sq(un);
+    for (size_t j = 0; j < un; j++) sq[j] = std::sqrt(infl[j]);
+    HIPCHK(c, obs.upload(c->stream, infl, at_infl, un));
+    HIPCHK(c, obs.upload(c->stream, sq.data(), at_sq, un));
+  }
+  MTSolveArgs a;
+  a.nmember = nmember; a.ncol = ncol; a.max_sweeps = c->tune.transform_sweeps; a.obs_off = ints.get(); a.hx = obs.get(); a.yobs = obs.get() + at_y;
+  a.rinv = obs.get() + at_r; a.infl = infl ? obs.get() + at_infl : nullptr; a.sqrt_infl = infl ? obs.get() + at_sq : nullptr;
+  a.T = fresh.get(); a.info = ints.get() + un + 1;
+  // the solve touches no model table, but the transform it replaces may still be read by an apply queued on the stream: it is
+  // queued there too, and the call waits for it
+  HIPCHK(c, timer.begin(c->stream));
+  HIPCHK(c, transform_solve(c->stream, a));
+  HIPCHK(c, timer.end(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (info) HIPCHK(c, ints.download(c->stream, info, un + 1, un));
+  d.d_transform = std::move(fresh);                // the old one goes with `fresh`
+  d.tf_nmember = nmember; d.tf_ncol = ncol;
+  float ms = 0;
+  if (timer.elapsed(&ms))
+    fprintf(stderr, "[vicgpu] member_transform_solve: %d members, %d columns, %d observations: %.4f ms on the device\n", nmember, ncol, nobs, ms);
+  return VICGPU_OK;
+}
+
+int vicgpu_member_transform_set(vicgpu_ctx* c, int nmember, int ncol, const double* T) {
+  const int r = transform_sizes_check(c, nmember, ncol);
+  if (r != VICGPU_OK) return r;
+  if (!T) return VICGPU_ERR_ARG;
+  const size_t count = (size_t)ncol * nmember * nmember;
+  for (size_t i = 0; i < count; i++)
+    if (!std::isfinite(T[i])) {
+      c->err = "member_transform_set: column " + std::to_string(i / ((size_t)nmember * nmember)) + ": a weight is not finite";
+      return VICGPU_ERR_ARG;
+    }
+  Domain& d = c->dom;
+  HIPCHK(c, hipSetDevice(c->device));
+  DevBuf<double> fresh;
+  HIPCHK(c, fresh.alloc(count));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // an apply queued earlier may still read the transform this one replaces
+  HIPCHK(c, fresh.upload(c->stream, T));
+  d.d_transform = std::move(fresh);
+  d.tf_nmember = nmember; d.tf_ncol = ncol;
+  return VICGPU_OK;
+}
+
+int vicgpu_member_transform_get(vicgpu_ctx* c, int* nmember, int* ncol, double* T) {
+  if (!c) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready || !c->dom.d_transform) return VICGPU_ERR_STATE;
+  const Domain& d = c->dom;
+  if (nmember) *nmember = d.tf_nmember;
+  if (ncol) *ncol = d.tf_ncol;
+  if (!T) return VICGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, d.d_transform.download(c->stream, T));
+  return VICGPU_OK;
+}
+
+// Everything the call allocates is allocated before anything is queued: one list block [rows][destination HRUs][their cells]
+// [their positions] and the stage.
+int vicgpu_member_transform_apply(vicgpu_ctx* c, int nrow, const int* rows, int n, const int* cols) {
+  if (!c || nrow < 0 || n < 0) return VICGPU_ERR_ARG;
+  if (!c->dom.domain_ready || !c->dom.d_transform) return VICGPU_ERR_STATE;
+  if (nrow == 0 || n == 0) return VICGPU_OK;
+  if (!rows) return VICGPU_ERR_ARG;
+  Domain& d = c->dom;
+  const int M = d.tf_nmember, ncol = d.tf_ncol;
+  if (d.cell_class.empty()) d.cell_class = copy_cell_classes(d.ncell, d.nhru, d.cell_off.data(), d.cell_list.data(), d.copy_key.data(), COPY_NKEY);
+  // every list is checked here, before the first write
+  TransformPlan& p = d.transform_plan;             // kept with the domain: the next call reuses its memory
+  plan_transform_apply(p, M, ncol, d.nhru, d.cell_off.data(), d.cell_list.data(), d.copy_key.data(), COPY_NKEY, d.cell_class.data(),
+                       (int)VICGPU_SD_NROW(c->o.Nnode), nrow, rows, n, cols);
+  if (p.fault != MT_OK) { c->err = transform_fault_text(p); return VICGPU_ERR_ARG; }
+  const int nh = (int)p.size();
+  if (nh == 0) return VICGPU_OK;                   // columns without HRUs
+  HIPCHK(c, hipSetDevice(c->device));
+  DevBuf<int> lists;
+  DevBuf<double> stage;
+  const size_t un = (size_t)nh;
+  HIPCHK(c, lists.alloc((size_t)nrow + 3 * un));
+  const int rpp = rows_per_pass((size_t)c->tune.copy_stage_mb << 20, un, sizeof(double), nrow);
+  HIPCHK(c, stage.alloc((size_t)rpp * un));
+  TransformLists l;
+  l.rows = lists.get(); l.hru = l.rows + nrow; l.cell = l.hru + nh; l.pos = l.cell + nh; l.cell_off = d.d_cell_off; l.cell_list = d.d_cell_list;
+  // the context's stream follows every step queued so far (with the finite-difference pipeline it waits for every chunk's
+  // `done` event, step_impl) and precedes every step queued later: the transform is queued there
+  StreamTimer timer;               // tuning (VICGPU_STATS): the kernels' own time
+  HIPCHK(c, timer.create(c->tune.stats));
+  HIPCHK(c, lists.upload(c->stream, rows, 0, (size_t)nrow));
+  HIPCHK(c, lists.upload(c->stream, p.hru.data(), (size_t)nrow, un));
+  HIPCHK(c, lists.upload(c->stream, p.cell.data(), (size_t)nrow + un, un));
+  HIPCHK(c, lists.upload(c->stream, p.pos.data(), (size_t)nrow + 2 * un, un));
+  HIPCHK(c, timer.begin(c->stream));
+  HIPCHK(c, transform_apply_staged(c->stream, d.d_sd, (size_t)d.nhru, l, M, ncol, d.d_transform, nrow, nh, stage, rpp));
+  HIPCHK(c, timer.end(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the lists and the stage are released when the call returns
+  float ms = 0;
+  if (timer.elapsed(&ms))
+    fprintf(stderr, "[vicgpu] member_transform_apply: %d members, %d columns, %d HRUs, %d rows, %d passes, %zu bytes written: %.4f ms on the device\n", M,
+            n, nh, nrow, (nrow + rpp - 1) / rpp, sizeof(double) * nrow * un, ms);
   return VICGPU_OK;
 }
 
